@@ -23,13 +23,25 @@ Each rank generates its contig ranges before the GPU is touched (synth.generate_
 every chunk from its own seed, in parallel worker processes).  cfg2 / cfg3 / cfg5 stay
 available as the main workload with --config.
 
-Extra keys on the line (rank 0, N=1): `cpu_baseline` (the oracle port on 1 core, on the
+A plain run does what the main line needs and no more: generate, upload, W untimed and K
+timed passes, the line (`value`, `ms_per_step`, the calls, the phase times and the dominant
+kernel's algorithmic roofline of those same passes).  --full adds every other leg: `weak`
+(N > 1), `strong_share_projection` (N = 1), the k2 leg, `ops_roofline`, the PMC-file figures
+(`roofline.traffic`, `roofline.valu`, the k2 leg's) and the extra keys below; the options
+that shape or disable those legs apply with it.
+
+--dump-outputs DIR writes the wf_result records of the last timed pass as DIR/<field>.npy
+(dump_outputs: float32 / float64, a seeded contig sample of a large batch, under 64 MB), so
+two builds can be compared record for record: the inputs are the same every run.
+
+Extra keys on the line with --full (rank 0, N=1): `cpu_baseline` (the oracle port on 1 core, on the
 job's cores in parallel processes over disjoint shards, and its explain_two pair rate on a
 stress contig), `pcie_inclusive` (scope ii: host arrays -> wf_score host mode -> host
 results), `cli_end_to_end` (scope iii: text files -> `python -m waafle_amd.orgscorer` ->
 TSVs, cfg2 and cfg3).
 
     python bench.py [--gpus N --steps K --warmup W] [--config cfg2|cfg3|cfg4|cfg5]
+                    [--full] [--dump-outputs DIR]
 """
 import argparse
 import ctypes as C
@@ -55,6 +67,12 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="cfg4")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg (weak scaling, share projection, k2 leg, op "
+                         "roofline, PMC-file figures, CPU baselines, host-array and CLI scopes); "
+                         "their own options below apply only with it")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the records of the last timed pass as DIR/<name>.npy")
     ap.add_argument("--contigs", type=int, default=None, help="override total contigs")
     ap.add_argument("--lds-bytes", type=int, default=None)
     ap.add_argument("--mode", default=None, choices=["level0", "waves", "staged"],
@@ -92,7 +110,12 @@ def parse_args():
                     help="FETCH/WRITE of the k2 leg's kernels (scripts/pmc_k2_r5.sh)")
     ap.add_argument("--k2-pmc-json", default=os.path.join(PROFILES, "r06", "k2_pmc.json"),
                     help="PMC VALU counts of the k2 leg's kernels (rocprofv3 --pmc, optional)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:         # a plain run: set up, warm up, time the steps, print the line
+        args.cpu_sample = args.cpu_parallel = args.cpu_k2_clades = 0
+        args.e2e, args.shares = "", ""
+        args.pcie = args.k2_contigs = args.weak = 0
+    return args
 
 
 def algorithmic_bytes(batch):
@@ -324,7 +347,8 @@ class DeviceBatch:
         if min_scov is not None:
             from waafle_amd import engine
             self.d["hit_key"] = torch.from_numpy(engine.hit_keys(batch, min_scov).view(np.int32)).to(dev)
-        e = lambda n, t: torch.empty(max(n, 1), dtype=t, device=dev)
+        # zeroed as engine.Results.empty: what a pass leaves unwritten reads the same every run
+        e = lambda n, t: torch.zeros(max(n, 1), dtype=t, device=dev)
         self.out = {
             "call": e(N, torch.int8), "crit": e(N, torch.float64), "rank": e(N, torch.float64),
             "clade1": e(N, torch.int32), "clade2": e(N, torch.int32),
@@ -345,6 +369,49 @@ class DeviceBatch:
 
     def host(self, f):
         return self.out[f].cpu().numpy()
+
+
+DUMP_CONTIGS = 200_000         # --dump-outputs: contigs sampled from a larger batch
+DUMP_MELD = 4_000_000          # and the meld ids kept (in contig order)
+
+
+def dump_outputs(db, batch, outdir, suffix=""):
+    """--dump-outputs: the wf_result records the last timed pass left in `db`, as
+    <outdir>/<field><suffix>.npy.  A batch of more than DUMP_CONTIGS contigs is sampled (the
+    same seeded, sorted contig indices every run: `contig`); per-contig fields are rows of that
+    sample, `synteny` / `annot_hit` the sample's loci back to back (`loc_off`: their CSR
+    offsets), `meld` the n_meld1 + n_meld2 ids of each sampled contig back to back.  Integer
+    fields that fit float32 exactly are float32, the others float64: under 64 MB in all."""
+    import torch
+    N = batch.n_contigs
+    sel = np.arange(N, dtype=np.int64)
+    if N > DUMP_CONTIGS:
+        sel = np.sort(np.random.default_rng(0).choice(N, DUMP_CONTIGS, replace=False)).astype(np.int64)
+    dev = db.out["call"].device
+
+    def take(f, idx):
+        return db.out[f][torch.from_numpy(idx).to(dev)].cpu().numpy()
+
+    def ranges(start, count):           # start[i] .. start[i] + count[i], back to back
+        off = np.concatenate([[0], np.cumsum(count)]).astype(np.int64)
+        return np.repeat(start - off[:-1], count) + np.arange(off[-1], dtype=np.int64), off
+
+    arrays = {"contig": sel.astype(np.float64)}
+    for f in ("call", "clade1", "clade2", "direction", "iterations", "n_meld1", "n_meld2", "status"):
+        arrays[f] = take(f, sel).astype(np.float32)
+    for f in ("crit", "rank", "pair_evals", "need_bytes"):
+        arrays[f] = take(f, sel).astype(np.float64)
+    loci, loff = ranges(batch.loc_off[sel].astype(np.int64), np.diff(batch.loc_off)[sel].astype(np.int64))
+    arrays["loc_off"] = loff.astype(np.float64)
+    arrays["synteny"] = take("synteny", loci).astype(np.float32)
+    arrays["annot_hit"] = take("annot_hit", loci).astype(np.float64)
+    n_meld = arrays["n_meld1"].astype(np.int64) + arrays["n_meld2"].astype(np.int64)
+    n_meld = np.clip(n_meld, 0, 2 * np.diff(batch.hit_off)[sel].astype(np.int64) + 2)   # a contig's room
+    melds, _ = ranges(2 * batch.hit_off[sel].astype(np.int64) + 2 * sel, n_meld)
+    arrays["meld"] = take("meld", melds[:DUMP_MELD]).astype(np.float32)
+    os.makedirs(outdir, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(outdir, name + suffix + ".npy"), arr)
 
 
 def timed_passes(so, h, chk, db, params, steps, warmup, dist, dev, cdev=None):
@@ -598,6 +665,8 @@ def main():
     db = DeviceBatch(batch, dev, params.min_scov)
     elapsed, tm = timed_passes(so, h, chk, db, params, args.steps, args.warmup, dist, dev, cdev)
     calls, pe, iters = db.host("call"), db.host("pair_evals"), db.host("iterations")
+    if args.dump_outputs:
+        dump_outputs(db, batch, args.dump_outputs, "" if rank == 0 else "_rank{}".format(rank))
     del db
     torch.cuda.empty_cache()
     weak = None
@@ -652,26 +721,31 @@ def main():
     b_alg = algorithmic_bytes(batch)
     achieved = b_dom / (dom_ms * 1e-3) / 1e9
     achieved_pass = b_alg / (pass_ms * 1e-3) / 1e9
-    # SURVEY 8(d)'s op roofline of the whole pass (this rank's contigs)
-    ops_s, ops_n = ops_site(batch, tax.parent, pdict, iters)
-    t_hbm, t_ops = b_alg / (HBM_PEAK_GBS * 1e9), (ops_s + k2_counts["ops_pair"]) / OPS_PEAK
-    ops_roofline = {
-        "rule": "SURVEY 8(d): roofline_time = max(B_alg / 8.0e12 B/s, OPS_alg / 3.93e13 op/s), OPS_alg "
-                "= OPS_site + OPS_pair; achieved = roofline_time / the pass time",
-        "b_alg": b_alg, "ops_site": ops_s, "ops_pair": k2_counts["ops_pair"],
-        "ops_site_rule": "sum over evaluated levels of len(locus) per (clade, locus) with an attached hit "
-                         "(the reference's site updates); numpy attachment rule on the first {} contigs, "
-                         "scaled".format(ops_n),
-        "t_hbm_ms": t_hbm * 1e3, "t_ops_ms": t_ops * 1e3, "roofline_time_ms": max(t_hbm, t_ops) * 1e3,
-        "pass_ms": pass_ms, "bound": "ops" if t_ops > t_hbm else "hbm",
-        "achieved": max(t_hbm, t_ops) * 1e3 / pass_ms,
-        "note": "counts the reference's per-site work; the closed-form means and the mask-class "
-                "pair search do far less of it"}
-    lib_sha = file_sha(L.LIB_PATH)
+    # SURVEY 8(d)'s op roofline of the whole pass (this rank's contigs); its op count is
+    # seconds of numpy on the host, so --full only
+    ops_roofline = None
+    if args.full:
+        ops_s, ops_n = ops_site(batch, tax.parent, pdict, iters)
+        t_hbm, t_ops = b_alg / (HBM_PEAK_GBS * 1e9), (ops_s + k2_counts["ops_pair"]) / OPS_PEAK
+        ops_roofline = {
+            "rule": "SURVEY 8(d): roofline_time = max(B_alg / 8.0e12 B/s, OPS_alg / 3.93e13 op/s), OPS_alg "
+                    "= OPS_site + OPS_pair; achieved = roofline_time / the pass time",
+            "b_alg": b_alg, "ops_site": ops_s, "ops_pair": k2_counts["ops_pair"],
+            "ops_site_rule": "sum over evaluated levels of len(locus) per (clade, locus) with an attached hit "
+                             "(the reference's site updates); numpy attachment rule on the first {} contigs, "
+                             "scaled".format(ops_n),
+            "t_hbm_ms": t_hbm * 1e3, "t_ops_ms": t_ops * 1e3, "roofline_time_ms": max(t_hbm, t_ops) * 1e3,
+            "pass_ms": pass_ms, "bound": "ops" if t_ops > t_hbm else "hbm",
+            "achieved": max(t_hbm, t_ops) * 1e3 / pass_ms,
+            "note": "counts the reference's per-site work; the closed-form means and the mask-class "
+                    "pair search do far less of it"}
+    lib_sha = file_sha(L.LIB_PATH) if args.full else None
 
     def pmc_file(path, kind):
         """A PMC summary of this config, contig count, dominant kernel and library build, or
         (None, why not)."""
+        if not args.full:
+            return None, "counters of runs of their own: with --full"
         if not path or not os.path.exists(path):
             return None, "no {} file".format(kind)
         with open(path) as fh:

@@ -10,5 +10,5 @@ fi
 if [ "${STAMPS:-1}" = 1 ]; then
   WAAFLE_HIP_LIB=waafle_amd/libwaafle_hip_stamps.so timeout -k 10 300 python scripts/wave_stamps.py > $O/stamps.json 2> $O/stamps.err || exit $?
 fi
-timeout -k 10 300 python bench.py --cpu-sample 0 --e2e= --pcie 0 ${BENCH_ARGS:---k2-contigs 0} > $O/bench.json 2> $O/bench.err || exit $?
+timeout -k 10 300 python bench.py --full --cpu-sample 0 --e2e= --pcie 0 ${BENCH_ARGS:---k2-contigs 0} > $O/bench.json 2> $O/bench.err || exit $?
 python scripts/show_bench.py $O/bench.json

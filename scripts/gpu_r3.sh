@@ -13,20 +13,20 @@ if [ "${SKIP_TESTS:-0}" != 1 ]; then
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || exit $?
 fi
 if [ "${BENCH:-1}" = 1 ]; then
-  timeout -k 10 900 python bench.py ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err || exit $?
+  timeout -k 10 900 python bench.py --full ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err || exit $?
 fi
 if [ -n "${AB:-}" ]; then
   IFS=';' read -ra runs <<< "$AB"
   for r in "${runs[@]}"; do
     name=${r%%=*}; args=${r#*=}
-    timeout -k 10 600 python bench.py $QUICK $args > $O/ab_$name.json 2> $O/ab_$name.err || exit $?
+    timeout -k 10 600 python bench.py --full $QUICK $args > $O/ab_$name.json 2> $O/ab_$name.err || exit $?
   done
 fi
 for v in ${VARIANTS:-}; do
-  WAAFLE_HIP_LIB=waafle_amd/libwaafle_hip_$v.so timeout -k 10 600 python bench.py $QUICK --k2-contigs 0 --steps 5 > $O/var_$v.json 2> $O/var_$v.err || exit $?
+  WAAFLE_HIP_LIB=waafle_amd/libwaafle_hip_$v.so timeout -k 10 600 python bench.py --full $QUICK --k2-contigs 0 --steps 5 > $O/var_$v.json 2> $O/var_$v.err || exit $?
 done
 if [ "${PROF:-1}" = 1 ]; then
-  timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/prof5 -o run --output-format csv -- python3 bench.py --config cfg5 --contigs 6250 --k2-contigs 0 $QUICK --steps 4 --warmup 1 ${PROF_ARGS:-} > $O/prof5.json 2> $O/prof5.err || exit $?
-  timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/prof4 -o run --output-format csv -- python3 bench.py --k2-contigs 0 $QUICK --steps 4 --warmup 1 ${PROF_ARGS:-} > $O/prof4.json 2> $O/prof4.err || exit $?
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/prof5 -o run --output-format csv -- python3 bench.py --full --config cfg5 --contigs 6250 --k2-contigs 0 $QUICK --steps 4 --warmup 1 ${PROF_ARGS:-} > $O/prof5.json 2> $O/prof5.err || exit $?
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/prof4 -o run --output-format csv -- python3 bench.py --full --k2-contigs 0 $QUICK --steps 4 --warmup 1 ${PROF_ARGS:-} > $O/prof4.json 2> $O/prof4.err || exit $?
 fi
 echo done

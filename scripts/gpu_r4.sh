@@ -16,6 +16,6 @@ if [ -n "${TESTS:-}" ]; then
   [ $rc -eq 0 ] || exit $rc
 fi
 if [ "${BENCH:-1}" = 1 ]; then
-  timeout -k 10 300 python bench.py --cpu-sample 0 --e2e= --pcie 0 ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --cpu-sample 0 --e2e= --pcie 0 ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
   python scripts/show_bench.py $O/bench.json
 fi

@@ -20,7 +20,7 @@ if [ -n "${AB:-}" ]; then
   for rep in $(seq 1 ${REPS:-2}); do
     for v in $AB; do
       if [ "$v" = prod ]; then lib=waafle_amd/libwaafle_hip.so; else lib=waafle_amd/libwaafle_hip_$v.so; fi
-      WAAFLE_HIP_LIB=$lib timeout -k 10 300 python3 bench.py $Q > $O/${v}_$rep.json 2> $O/${v}_$rep.err || { tail -5 $O/${v}_$rep.err; exit 1; }
+      WAAFLE_HIP_LIB=$lib timeout -k 10 300 python3 bench.py --full $Q > $O/${v}_$rep.json 2> $O/${v}_$rep.err || { tail -5 $O/${v}_$rep.err; exit 1; }
       echo "$v rep $rep: $(python3 scripts/show_bench.py $O/${v}_$rep.json | tr '\n' ' ')"
     done
   done

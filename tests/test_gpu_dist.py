@@ -86,7 +86,7 @@ def test_bench_two_ranks_on_one_device(tmp_path):
     out = tmp_path / "bench2.json"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+           os.path.join(REPO, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1",
            "--contigs", "20000", "--k2-contigs", "200", "--k2-steps", "1", "--cpu-sample", "0",
            "--e2e=", "--pcie", "0", "--backend", "gloo", "--device-map", "0,0"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
@@ -194,7 +194,7 @@ def test_bench_one_gpu_share_projection(tmp_path):
     """bench.py at N = 1 times every strong-scaling share of the workload alone on the GPU
     (`strong_share_projection`): N shares per N covering the contigs, projected value = the
     contigs / the slowest share's pass, efficiency = t(whole) / (N x slowest share)."""
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--full", "--steps", "2", "--warmup", "1",
            "--contigs", "20000", "--k2-contigs", "0", "--cpu-sample", "0", "--e2e=", "--pcie", "0",
            "--shares", "2,4"]
     run = subprocess.run(cmd, capture_output=True, text=True, timeout=420, cwd=REPO)
