@@ -27,7 +27,8 @@ extern "C" {
 #define WF_ABI_VERSION 6   /* 4: WF_OPT_SPARSE_BIG 0/1 retired, WF_PHASE_ROLLUP, WF_OPT_WAVE_TWO / _DUMP_CAP;
                                  5: WF_OPT_TRIAGE, WF_PHASE_TRIAGE;
                                  6: wf_batch.hit_key (packed hit record), wf_pack_hit_keys;
-                                    WF_OPT_WAVE_TWO 0 (the round-3 hand-over flow) retired */
+                                    WF_OPT_WAVE_TWO 0 (the round-3 hand-over flow) retired;
+                                    still 6 (additive): wf_map_index, wf_map_pairs */
 
 enum wf_status {
   WF_OK = 0,
@@ -289,6 +290,62 @@ typedef struct wf_jn_result {   /* same residency as the batch */
 } wf_jn_result;
 
 int wf_junctions(wf_ctx* ctx, const wf_jn_batch* batch, const wf_jn_params* params, wf_jn_result* out);
+
+/* ---- paired-read mapper (the read input of waafle_junctions, in place of bowtie2) -------
+ * A deterministic seed-and-verify ungapped mapper; DESIGN.md §11 states the rule in full.
+ * Bases are upper-cased and every byte other than A, C, G, T is N, which mismatches
+ * everything.  wf_map_index keeps, in the context, the contigs as two bit planes plus an N
+ * plane and the sorted (S-mer, position) index of every forward-strand S-mer that lies in one
+ * contig and holds no N; a second call replaces the first index.  wf_map_pairs maps read
+ * pairs against it: each mate as given (+) and reverse-complemented (-), seeds at offsets
+ * 0, S, 2S, ... (at most 16), seeds with more than max_occ occurrences unused, ungapped
+ * alignments inside one contig with at most max_mm mismatches, and of the concordant pairs
+ * (same contig, opposite strands, no dovetail, min_insert <= fragment <= max_insert) the
+ * one with the least (mm1 + mm2, contig, + mate's position, fragment, mate-1 strand).
+ * No gaps, no clipping, no MAPQ: reads with indels stay unaligned. */
+typedef struct wf_map_params {
+  int32_t seed_len;           /* S, 12..32 (default 20) */
+  int32_t max_occ;            /* 1..64 (default 16) */
+  int32_t max_mm;             /* 0..32 mismatches per mate (default 4) */
+  int32_t _pad;
+  int64_t min_insert;         /* fragment length bounds (defaults 0, 500) */
+  int64_t max_insert;
+} wf_map_params;
+
+typedef struct wf_map_contigs { /* host memory */
+  int32_t n_contigs;
+  int32_t _pad;
+  const char* seq;            /* [off[n_contigs]] the contigs' ASCII bases, concatenated */
+  const int64_t* off;         /* [n_contigs + 1] off[0] = 0; off[n_contigs] < 2^31 - 1024,
+                                 else WF_E_TOOBIG */
+} wf_map_contigs;
+
+typedef struct wf_map_reads {
+  int64_t n_pairs;            /* < 2^31 per call */
+  int32_t device_resident;    /* 1: device pointers (reads and result); 0: host arrays.  The
+                                 offsets are read back and checked either way, so the call
+                                 synchronises */
+  int32_t _pad;
+  const char* seq1;           /* mate 1: ASCII bases, concatenated */
+  const int64_t* off1;        /* [n_pairs + 1]; a read longer than 512: WF_E_BADINPUT */
+  const char* seq2;           /* mate 2 */
+  const int64_t* off2;
+} wf_map_reads;
+
+typedef struct wf_map_result {  /* [n_pairs] each, same residency as the reads */
+  int32_t* contig;            /* contig index, -1: unaligned (the other fields are then 0) */
+  int32_t* pos1;              /* 1-based leftmost contig position of mate 1 */
+  int32_t* pos2;              /* ... of mate 2 */
+  uint8_t* strand1;           /* 0: mate 1 on +, mate 2 on -; 1: the reverse */
+  uint8_t* mm1;               /* mismatches of mate 1 */
+  uint8_t* mm2;
+} wf_map_result;
+
+/* params: seed_len and max_occ (the other fields are not read) */
+int wf_map_index(wf_ctx* ctx, const wf_map_contigs* contigs, const wf_map_params* params);
+/* params: seed_len and max_occ must equal the index's (WF_E_BADINPUT); WF_E_STATE before
+   wf_map_index */
+int wf_map_pairs(wf_ctx* ctx, const wf_map_reads* reads, const wf_map_params* params, wf_map_result* out);
 
 /* ---- --write-details (orgscorer.py:766-812, 931-937) --------------------------------
  * With details on, the next wf_score (staged mode) also records, for every roll-up level,

@@ -51,6 +51,7 @@ struct wf_ctx {
   int64_t dump_cap = 0;            // wf_set_option(WF_OPT_DUMP_CAP), 0: the default size
   int triage = 1;                  // wf_set_option(WF_OPT_TRIAGE)
   wf::StagedState* staged = nullptr;
+  wf::MapState* map = nullptr;     // paired-read mapper: its index and staging (wf_map_index)
   // --write-details
   bool details_on = false;
   wf::DetailsSink det;
@@ -225,6 +226,7 @@ void wf_free(wf_ctx* ctx) {
                     &ctx->r_pairs, &ctx->r_status, &ctx->r_need, &ctx->r_ppot};
   for (DevBuf* b : bufs) release(*b);
   if (ctx->staged) wf::staged_destroy(ctx->staged);
+  if (ctx->map) wf::map_destroy(ctx->map);
   for (hipEvent_t ev : ctx->ev_pool) (void)hipEventDestroy(ev);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
   delete ctx;
@@ -682,6 +684,60 @@ int wf_junctions(wf_ctx* ctx, const wf_jn_batch* b, const wf_jn_params* p, wf_jn
   if (overflow)
     return fail(ctx, WF_E_NOMEM, "%u read pairs hit loci more than 64 apart (pair_mask holds 64)", overflow);
   return WF_OK;
+}
+
+static int check_map_params(wf_ctx* ctx, const wf_map_params* p, bool rule) {
+  if (p->seed_len < 12 || p->seed_len > 32) return fail(ctx, WF_E_BADINPUT, "seed_len %d outside 12..32", p->seed_len);
+  if (p->max_occ < 1 || p->max_occ > 64) return fail(ctx, WF_E_BADINPUT, "max_occ %d outside 1..64", p->max_occ);
+  if (!rule) return WF_OK;
+  if (p->max_mm < 0 || p->max_mm > 32) return fail(ctx, WF_E_BADINPUT, "max_mm %d outside 0..32", p->max_mm);
+  if (p->min_insert < 0 || p->max_insert < p->min_insert || p->max_insert >= ((int64_t)1 << 31))
+    return fail(ctx, WF_E_BADINPUT, "insert bounds must satisfy 0 <= min <= max < 2^31");
+  return WF_OK;
+}
+
+int wf_map_index(wf_ctx* ctx, const wf_map_contigs* c, const wf_map_params* p) {
+  if (!ctx) return WF_E_BADINPUT;
+  if (!c || !p) return fail(ctx, WF_E_BADINPUT, "null contigs/params");
+  if (c->n_contigs < 0) return fail(ctx, WF_E_BADINPUT, "negative sizes");
+  if (c->n_contigs > 0 && !c->off) return fail(ctx, WF_E_BADINPUT, "null contig offsets");
+  int rc = check_map_params(ctx, p, false);
+  if (rc) return rc;
+  if (c->n_contigs > 0) {
+    if (c->off[0] != 0) return fail(ctx, WF_E_BADINPUT, "contig offsets must start at 0");
+    for (int32_t i = 0; i < c->n_contigs; ++i)
+      if (c->off[i + 1] < c->off[i]) return fail(ctx, WF_E_BADINPUT, "contig offsets decrease at contig %d", i);
+    if (c->off[c->n_contigs] > 0 && !c->seq) return fail(ctx, WF_E_BADINPUT, "null contig bases");
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (!ctx->map) ctx->map = wf::map_create();
+  std::string err;
+  rc = wf::map_index(ctx->map, c->seq, c->off, c->n_contigs, p->seed_len, p->max_occ, ctx->stream, &err);
+  return rc ? fail(ctx, rc, "%s", err.c_str()) : WF_OK;
+}
+
+int wf_map_pairs(wf_ctx* ctx, const wf_map_reads* rd, const wf_map_params* p, wf_map_result* r) {
+  if (!ctx) return WF_E_BADINPUT;
+  if (!rd || !p || !r) return fail(ctx, WF_E_BADINPUT, "null reads/params/result");
+  if (rd->n_pairs < 0 || rd->n_pairs >= ((int64_t)1 << 31)) return fail(ctx, WF_E_BADINPUT, "n_pairs outside [0, 2^31)");
+  int rc = check_map_params(ctx, p, true);
+  if (rc) return rc;
+  int S = 0, occ = 0;
+  if (!wf::map_index_params(ctx->map, &S, &occ)) return fail(ctx, WF_E_STATE, "wf_map_pairs before wf_map_index");
+  if (S != p->seed_len || occ != p->max_occ)
+    return fail(ctx, WF_E_BADINPUT, "seed_len %d / max_occ %d differ from the index's %d / %d", p->seed_len,
+                p->max_occ, S, occ);
+  if (rd->n_pairs == 0) return WF_OK;
+  if (!rd->off1 || !rd->off2 || !rd->seq1 || !rd->seq2) return fail(ctx, WF_E_BADINPUT, "null read arrays");
+  if (!r->contig || !r->pos1 || !r->pos2 || !r->strand1 || !r->mm1 || !r->mm2)
+    return fail(ctx, WF_E_BADINPUT, "null result arrays");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const wf::MapReads reads{rd->n_pairs, rd->device_resident, rd->seq1, rd->off1, rd->seq2, rd->off2};
+  const wf::MapRule rule{p->max_occ, p->max_mm, p->min_insert, p->max_insert};
+  const wf::MapOut out{r->contig, r->pos1, r->pos2, r->strand1, r->mm1, r->mm2};
+  std::string err;
+  rc = wf::map_pairs(ctx->map, reads, rule, out, ctx->stream, &err);
+  return rc ? fail(ctx, rc, "%s", err.c_str()) : WF_OK;
 }
 
 int wf_details_enable(wf_ctx* ctx, int on) {

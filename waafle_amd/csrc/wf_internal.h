@@ -166,6 +166,23 @@ struct JnArgs {
 int junctions_run(const JnArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s, std::string* err);
 size_t junctions_tmp_bytes(int64_t n_sites);
 
+// paired-read mapper (wf_map.hip): the index of one contig set, kept between calls, and the
+// per-pair seed-and-verify kernel.  0, or -1 / -2 / -7 with the message in *err.
+struct MapState;
+struct MapReads {
+  int64_t n_pairs; int device_resident;
+  const char* seq1; const int64_t* off1; const char* seq2; const int64_t* off2;
+};
+struct MapRule { int max_occ, max_mm; int64_t min_insert, max_insert; };
+struct MapOut { int32_t* contig; int32_t* pos1; int32_t* pos2; uint8_t* strand1; uint8_t* mm1; uint8_t* mm2; };
+MapState* map_create();
+void map_destroy(MapState* st);
+int map_index_params(const MapState* st, int* seed_len, int* max_occ);   // 0: no index yet
+int map_index(MapState* st, const char* seq, const int64_t* off, int n_contigs, int seed_len, int max_occ,
+              hipStream_t s, std::string* err);                          // host arrays
+int map_pairs(MapState* st, const MapReads& rd, const MapRule& rule, const MapOut& out, hipStream_t s,
+              std::string* err);
+
 // --write-details: per roll-up level, the evaluated (active) contigs and the segment
 // records of the level, copied to the host (wf_staged.hip details_level)
 struct DetailsLevel {

@@ -310,6 +310,21 @@ def build_parser():
     g.add_argument("--resume", action="store_true",
                    help="if set, use existing .index and/or .sam if found\n[default: off]")
     g.add_argument("--gpu", type=int, default=0, help="device to run on (MI355X build)")
+    g = ap.add_argument_group("read mapper")
+    g.add_argument("--mapper", choices=["bowtie2", "native"], default="bowtie2",
+                   help="how --reads1/--reads2 are aligned: bowtie2 (as upstream), or the built-in\n"
+                        "ungapped seed-and-verify mapper on the GPU (not a bowtie2 clone)\n"
+                        "[default: bowtie2]")
+    g.add_argument("--seed-length", type=int, default=20, metavar="<int>",
+                   help="native mapper: seed length, 12..32\n[default: 20]")
+    g.add_argument("--max-seed-hits", type=int, default=16, metavar="<int>",
+                   help="native mapper: a seed with more occurrences is not used, 1..64\n[default: 16]")
+    g.add_argument("--max-mismatches", type=int, default=4, metavar="<int>",
+                   help="native mapper: mismatches allowed per mate, 0..32\n[default: 4]")
+    g.add_argument("--min-insert", type=int, default=0, metavar="<int>",
+                   help="native mapper: minimum fragment length\n[default: 0]")
+    g.add_argument("--max-insert", type=int, default=500, metavar="<int>",
+                   help="native mapper: maximum fragment length\n[default: 500]")
     return ap
 
 
@@ -325,22 +340,45 @@ def _bowtie2(args, p_index, p_sam):
             args.bowtie2, p_index, args.reads1, args.reads2, p_sam, args.threads), shell=True)
 
 
+def _native_map(args, p_sam):
+    """--mapper native: align the reads with the built-in mapper (mapper.py), write the SAM
+    file and return the aligned pairs' arrays (as read_pairs would read them back)."""
+    from . import mapper
+    inputs.say("Mapping reads with the built-in mapper to <{}>.".format(p_sam))
+    contigs = mapper.read_fasta(args.contigs)
+    pairs, total = mapper.map_pairs(contigs, args.reads1, args.reads2, sam_path=p_sam, device=args.gpu,
+                                    seed_length=args.seed_length, max_seed_hits=args.max_seed_hits,
+                                    max_mismatches=args.max_mismatches, min_insert=args.min_insert,
+                                    max_insert=args.max_insert)
+    inputs.say("Aligned {} of {} read pairs.".format(len(pairs[0]), total))
+    return pairs + ([],)
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     basename = args.basename or inputs.basename_of(args.contigs)
     p_sam = os.path.join(args.tmpdir, basename + ".sam")
+    pairs = None
     if args.sam is not None:
         p_sam = args.sam
         inputs.say("Using specified SAM file:", p_sam)
     elif args.reads1 is not None and args.reads2 is not None:
-        _bowtie2(args, os.path.join(args.tmpdir, basename + ".index"), p_sam)
+        if args.mapper == "native":
+            if not (args.resume and os.path.exists(p_sam)):
+                try:
+                    pairs = _native_map(args, p_sam)
+                except (inputs.InputError, OSError, L.WaafleHipError) as exc:
+                    die(str(exc))
+        else:
+            _bowtie2(args, os.path.join(args.tmpdir, basename + ".index"), p_sam)
     else:
         die("Must provide READS or SAM file.")
     try:
         lengths = inputs.read_contig_lengths(args.contigs)
         loci = read_contig_loci(args.gff)
         names = list(lengths)
-        pairs = read_pairs(p_sam, {n: i for i, n in enumerate(names)})
+        if pairs is None:
+            pairs = read_pairs(p_sam, {n: i for i, n in enumerate(names)})
     except (inputs.InputError, JunctionError, ValueError) as exc:
         die(str(exc))
     if pairs[5]:

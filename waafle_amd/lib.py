@@ -99,6 +99,25 @@ class WfJnResult(C.Structure):
                 ("pair_first", _P), ("pair_mask", _P)]
 
 
+class WfMapParams(C.Structure):
+    _fields_ = [("seed_len", C.c_int32), ("max_occ", C.c_int32), ("max_mm", C.c_int32),
+                ("_pad", C.c_int32), ("min_insert", C.c_int64), ("max_insert", C.c_int64)]
+
+
+class WfMapContigs(C.Structure):
+    _fields_ = [("n_contigs", C.c_int32), ("_pad", C.c_int32), ("seq", _P), ("off", _P)]
+
+
+class WfMapReads(C.Structure):
+    _fields_ = [("n_pairs", C.c_int64), ("device_resident", C.c_int32), ("_pad", C.c_int32),
+                ("seq1", _P), ("off1", _P), ("seq2", _P), ("off2", _P)]
+
+
+class WfMapResult(C.Structure):
+    _fields_ = [("contig", _P), ("pos1", _P), ("pos2", _P), ("strand1", _P), ("mm1", _P),
+                ("mm2", _P)]
+
+
 class WfDetails(C.Structure):
     _fields_ = [("n_evals", C.c_int64), ("eval_contig", _P), ("eval_level", _P),
                 ("n_segs", C.c_int64), ("seg_level", _P), ("seg_contig", _P), ("seg_clade", _P),
@@ -128,6 +147,9 @@ SIGNATURES = {
                               C.POINTER(WfGcResult)]),
     "wf_junctions": (C.c_int, [C.c_void_p, C.POINTER(WfJnBatch), C.POINTER(WfJnParams),
                                C.POINTER(WfJnResult)]),
+    "wf_map_index": (C.c_int, [C.c_void_p, C.POINTER(WfMapContigs), C.POINTER(WfMapParams)]),
+    "wf_map_pairs": (C.c_int, [C.c_void_p, C.POINTER(WfMapReads), C.POINTER(WfMapParams),
+                               C.POINTER(WfMapResult)]),
     "wf_details_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "wf_details_read": (C.c_int, [C.c_void_p, C.POINTER(WfDetails)]),
 }
