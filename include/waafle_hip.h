@@ -72,11 +72,14 @@ enum wf_mode { WF_MODE_STAGED = 0, WF_MODE_LEVEL0 = 2, WF_MODE_WAVES = 3 };
  * WF_OPT_ATT_LIMIT: hit-locus attachments the staged kernels accept in one wf_score call
  *   (default and maximum 2^31 - 1; more -> WF_E_TOOBIG and the call's records are not
  *   valid: score the batch in parts).  The wave forms hold a contig's attachments in LDS.
- * WF_OPT_WAVE_TWO (WF_MODE_LEVEL0): 1, the only value since ABI 6: the first wave form also
- *   decides explain_two (up to 64 potential clades, <= 63 loci) and carries the roll-up
- *   levels, one pass per level over the contigs still open; the rest goes to the
- *   segment-table decision (k_dump_sparse).  0 (every explain_two contig there and the
- *   roll-up levels in the staged kernels: the round-3 flow) is retired: WF_E_BADINPUT.
+ * WF_OPT_WAVE_TWO (WF_MODE_LEVEL0): the first wave form also prepares explain_two (up to 64
+ *   potential clades, <= 63 loci) and carries the roll-up levels, one pass per level over
+ *   the contigs still open; the rest goes to the segment-table decision (k_dump_sparse).
+ *   2 (default): a contig whose potential clades form no candidate pair is raised or stopped
+ *   by the wave itself, with no table; the others hand a compact table to k_dump_sparse.
+ *   1: every such contig hands its compact table over (a test setting, and the same-build
+ *   comparison arm).  0 (every explain_two contig to the whole-table decision and the roll-up
+ *   levels in the staged kernels: the round-3 flow) is retired: WF_E_BADINPUT.
  * WF_OPT_DUMP_CAP: segment-table entries of the wave form's hand-over buffer (default
  *   max(32 * contigs, 65536)); contigs past it go to the staged kernels (a test setting).
  * WF_OPT_TRIAGE (WF_MODE_LEVEL0 / _WAVES): 1 (default) a level-0 triage kernel first decides
@@ -196,7 +199,7 @@ enum wf_phase {
   WF_PHASE_HANDOVER = 5,      /* level 0 of the contigs the wave kernels hand over with
                                  their segment tables (k_dump_sparse) */
   WF_PHASE_ROLLUP = 6,        /* roll-up levels 1, 2, ... in the first wave form (with their
-                                 hand-overs), WF_OPT_WAVE_TWO 1 */
+                                 hand-overs), WF_OPT_WAVE_TWO 1 or 2 */
   WF_PHASE_TRIAGE = 7,        /* the level-0 triage kernel and the list of contigs it hands
                                  on (WF_OPT_TRIAGE 1); WF_PHASE_WAVES is then the first wave
                                  form's launch over that list */

@@ -50,6 +50,7 @@ struct wf_ctx {
   int64_t att_limit = (int64_t(1) << 31) - 1;   // wf_set_option(WF_OPT_ATT_LIMIT)
   int64_t dump_cap = 0;            // wf_set_option(WF_OPT_DUMP_CAP), 0: the default size
   int triage = 1;                  // wf_set_option(WF_OPT_TRIAGE)
+  int wave_two = 2;                // wf_set_option(WF_OPT_WAVE_TWO)
   wf::StagedState* staged = nullptr;
   wf::MapState* map = nullptr;     // paired-read mapper: its index and staging (wf_map_index)
   // --write-details
@@ -271,7 +272,8 @@ int wf_set_option(wf_ctx* ctx, int option, int64_t value) {
       ctx->att_limit = value;
       return WF_OK;
     case WF_OPT_WAVE_TWO:        // (0, the round-3 hand-over flow, retired in ABI 6)
-      if (value != 1) return fail(ctx, WF_E_BADINPUT, "WF_OPT_WAVE_TWO is 1 (0 is retired)");
+      if (value < 1 || value > 2) return fail(ctx, WF_E_BADINPUT, "WF_OPT_WAVE_TWO is 1 or 2 (0 is retired)");
+      ctx->wave_two = (int)value;
       return WF_OK;
     case WF_OPT_DUMP_CAP:
       if (value < 0 || value > (int64_t(1) << 31) - 4096)
@@ -395,7 +397,7 @@ static int run_kernels(wf_ctx* ctx, wf::KArgs& K, const wf_batch* b) {
   if (ctx->lds_set) wf::staged_set_lds(ctx->staged, ctx->lds_bytes);
   wf::staged_set_level0(ctx->staged, ctx->mode != WF_MODE_STAGED, ctx->mode == WF_MODE_WAVES);
   wf::staged_set_options(ctx->staged, ctx->sparse_big, ctx->att_limit, ctx->dump_cap,
-                         ctx->triage);
+                         ctx->triage, ctx->wave_two);
   std::pair<int, int> el{-1, -1};
   if (ctx->timing) {
     if (take_event_pair(ctx, ctx->ev_lds) < 0) return fail(ctx, WF_E_HIP, "hipEventCreate failed");

@@ -35,6 +35,29 @@ __device__ __forceinline__ void note_ppot(const KArgs& K, int c, int iteration, 
     K.ppot[c] = (int64_t)(((uint64_t)iteration << 40) | ((old & ((1ull << 40) - 1ull)) + (uint64_t)Pp));
 }
 
+// explain_two of the compact hand-over found no explanation (orgscorer.py:570-583): raise
+// (pend[c] = 2, the contig joins the next level; returns true), or stop at r__Root / after
+// kMaxIter levels with the unclassified record.  sp_two's tail (wf_sparse.h), and the first
+// wave form's own when it sees that no candidate pair exists (wf_fast.hip).  The whole wave
+// calls it.
+__device__ __forceinline__ bool e2_no_option(const KArgs& K, int c, int iteration, int64_t pair_evals, bool root,
+                                             int32_t* pend) {
+  const int lane = threadIdx.x & 63;
+  if (!root && iteration + 1 <= kMaxIter) {
+    if (lane == 0) {
+      pend[c] = 2;
+      K.pair_evals[c] = pair_evals;
+    }
+    return true;
+  }
+  if (lane == 0) {                                   // unclassified after evaluation
+    K.iters[c] = (int16_t)min(root ? iteration : iteration + 1, 32767);
+    K.pair_evals[c] = pair_evals;
+    K.status[c] = root ? 0 : WF_E_RUNAWAY;
+  }
+  return false;
+}
+
 struct Ctl {
   int A, A1, npow, S_n, P, Gu, Pp;
   int overflow, status, cnt, cnt2, p_unk, root_present, all_ignored;

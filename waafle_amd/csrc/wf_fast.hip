@@ -1091,6 +1091,8 @@ __global__ __launch_bounds__(64, FULL ? 2 : (ROLL ? kRollWaves : 4)) void k_wave
       uint64_t open = 0;
       int outcome = 0;                                 // 2: decided (or stopped) by explain_one
       bool compact_ok = false;                         // passes 4, 5 ran: explain_two's inputs only
+      int e2_np = 0;                                   // pass 4: the potential clades (<= 64), and
+      bool e2_pairs = false;                           // whether any two form a candidate pair
       // first form: the level's decision goes to k_dump_sparse with the whole segment table
       // (pass 6 evaluates the rest) instead of the staged kernels
       bool dump = false;
@@ -1351,6 +1353,8 @@ __global__ __launch_bounds__(64, FULL ? 2 : (ROLL ? kRollWaves : 4)) void k_wave
             if (lane < np0 && !member)
               for (int q = ph; q < ph + pcnt; ++q) rc[q] = (uint8_t)((rc[q] & 0x80) | 2);
             wave_sync();
+            e2_np = np0;
+            e2_pairs = __ballot(lane < np0 && member) != 0ull;
           }
           npp = 0;                                     // their parents (sister checks, :717-744)
           int npot = 0;
@@ -1575,6 +1579,21 @@ __global__ __launch_bounds__(64, FULL ? 2 : (ROLL ? kRollWaves : 4)) void k_wave
           rootp = __ballot(rootp) != 0ull;
           compact = n2 <= kE2Seg;
           if (compact) n_out = n2;
+        }
+        // WF_OPT_WAVE_TWO 2: a compact hand-over with no candidate pair is settled here, with
+        // no table and no sp_two wave.  Pass 4 holds the potential clades and their ">= k2"
+        // masks on the unmasked loci, so the candidate pairs are known (exact: its comment);
+        // without one explain_two has nothing to rank, and the contig is raised (onto the next
+        // level's list) or stops, as sp_two's tail and k_dump_sparse's finish would have it.
+        if (compact && S.wave_two == 2 && !e2_pairs) {
+          pair_evals += (int64_t)e2_np * (e2_np - 1) / 2;
+          if (lane == 0) note_ppot(K, c, iteration, e2_np);
+          const bool raised = e2_no_option(K, c, iteration, pair_evals, rootp, pend);
+          if (raised && lane == 0 && S.roll_next) S.roll_next[atomicAdd(S.roll_next_n, 1ull)] = c;
+          staged = raised;                             // raised: pend 2, its attachment counts stand
+          seed = raised;
+          WLAP(9);
+          break;
         }
         // the table: one 64-bit atomic gives the slot (high bits) and its first entry (low
         // 40), so slot k's entries start where slot k - 1's end

@@ -119,13 +119,14 @@ struct SArgs {
   // *roll_next_n); contigs that leave the wave forms count in *fail_ctr (pend 1)
   int32_t* anc;                  // [n_tax] ancestor of each name at this level (null: level 0)
   int n_tax;
-  int wave_two;                  // explain_two in the first form (else every such contig
-                                 // goes to k_dump_sparse with its segment table)
+  int wave_two;                  // WF_OPT_WAVE_TWO: 1 the first form hands explain_two's inputs to
+                                 // k_dump_sparse<1> as a compact table, 2 it also settles the
+                                 // ones with no candidate pair itself (0: whole tables only)
   int32_t* roll_next;            // contigs raised at this level (null: no wave levels)
   unsigned long long* roll_next_n;
   unsigned long long* fail_ctr;
   unsigned long long* dump_ctr_next;   // k_dump_sparse zeroes the next level's table counter
-  unsigned long long* wq;        // k_wave over a list: its contigs handed out one at a time by this
+  unsigned long long* wq;       // k_wave over a list: its contigs handed out one at a time by this
                                  // counter (zeroed per pass), else in static XCD order (null)
 };
 
@@ -228,7 +229,7 @@ void staged_set_lds(StagedState* st, int64_t bytes);
 // that outgrow the LDS arena, the attachments one call accepts (more: WF_E_TOOBIG), explain_two
 // and the roll-up levels in the first wave form, the hand-over buffer's size (0: default)
 void staged_set_options(StagedState* st, int sparse_big, int64_t att_limit, int64_t dump_cap,
-                        int triage);
+                        int triage, int wave_two);
 // per-phase timing (wf_phase): HIP events around each phase of each level, read back at the
 // end of every staged_score call into the accumulators (reset by staged_timing(st, on))
 void staged_timing(StagedState* st, bool on);

@@ -1388,18 +1388,7 @@ __device__ __forceinline__ bool sp_two(const SArgs& S, E2Shared& sh, int c, int 
   SLAP(5);
   // no explanation at this level (:570-583): raise, or stop at r__Root (the table is never
   // empty: explain_one ran on this contig's segments)
-  if (!root && iteration + 1 <= kMaxIter) {
-    if (lane == 0) {
-      S.seed_pend[c] = 2;
-      K.pair_evals[c] = pair_evals;
-    }
-    return true;
-  }
-  if (lane == 0) {                                   // unclassified after evaluation
-    K.iters[c] = (int16_t)min(root ? iteration : iteration + 1, 32767);
-    K.pair_evals[c] = pair_evals;
-    K.status[c] = root ? 0 : WF_E_RUNAWAY;
-  }
+  e2_no_option(K, c, iteration, pair_evals, root, S.seed_pend);
   return true;
 }
 

@@ -1870,6 +1870,7 @@ struct StagedState {
   int64_t att_limit = (int64_t(1) << 31) - 1;   // attachments per call (WF_OPT_ATT_LIMIT)
   int64_t dump_cap = 0;              // WF_OPT_DUMP_CAP (0: max(32 N, 65536))
   int triage = 1;                    // WF_OPT_TRIAGE: level-0 triage before the first wave form
+  int wave_two = 2;                  // WF_OPT_WAVE_TWO: 2 pairless hand-overs settled in the wave, 1 none
   Buf tri_list, tri_cnt;             // the contigs the triage hands on, and their count
   Buf wq;                            // roll-up launches' work-queue counters
   Buf roll0, roll1, roll_cnt, anc;   // wave levels: contig lists, per-level counts, ancestors
@@ -1938,8 +1939,10 @@ void staged_set_lds(StagedState* st, int64_t bytes) {
   st->dec_lds_fixed = true;
 }
 
-void staged_set_options(StagedState* st, int sparse_big, int64_t att_limit, int64_t dump_cap, int triage) {
+void staged_set_options(StagedState* st, int sparse_big, int64_t att_limit, int64_t dump_cap, int triage,
+                        int wave_two) {
   st->triage = triage;
+  st->wave_two = wave_two;
   st->sparse_big = sparse_big;
   st->att_limit = att_limit;
   st->dump_cap = dump_cap;
@@ -2309,7 +2312,7 @@ static int staged_run(StagedState* st, const KArgs& k, int n_tax, int max_loci, 
         ST_TRY(hipMemsetAsync(st->roll_cnt.p, 0, (kMaxIter + 3) * sizeof(unsigned long long), s));
         rcnt = st->roll_cnt.as<unsigned long long>();
         da.n_tax = n_tax;
-        da.wave_two = 1;
+        da.wave_two = st->wave_two;
         da.roll_next = st->roll1.as<int32_t>();     // level L appends to roll[(L + 1) & 1]
         da.roll_next_n = rcnt + 1;
         da.fail_ctr = rcnt + kMaxIter + 2;
