@@ -3,7 +3,11 @@ over the whole locus: spine + one (Q(B_d), Q(B_d + 1)) pair per depth, no leaf t
 pw_run_sum (any run [lo, hi): the split node, a suffix and a prefix path, whole siblings
 from the same pair chain, run_leaf at the path ends), restated line by line in Python and
 checked against numpy's pairwise tree (numpy/_core/src/umath/loops_utils.h.src
-pairwise_sum) -- for every buffer length, and on explicit arrays for partial runs."""
+pairwise_sum) -- for every buffer length, and on explicit arrays for partial runs.
+
+This checks the model: the restatement, not the device code, so an edit to wf_device.h that
+is not mirrored here leaves it green.  The device functions themselves are checked by
+tests/test_gpu_means.py (every locus length against np.mean, in every execution form)."""
 import random
 
 import numpy as np

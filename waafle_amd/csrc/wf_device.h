@@ -577,7 +577,8 @@ struct PackedLut {
 // Q(ceil(x/2))) one pair (Q(B_d), Q(B_d + 1)) per depth carries the whole tree: bottom pair
 // from seqsum captures (seqsum(v, x + 1) = seqsum(v, x) + v exactly), each pair above from
 // the one below, and the spine sum adds its left sibling's Q level by level.  Equal to the
-// leaf-table walk bit for bit for every n < 8192 (tests/test_pw_const.py checks the model).
+// leaf-table walk bit for bit for every n < 8192 (tests/test_pw_const.py checks a Python
+// restatement, the model; tests/test_gpu_means.py checks this code against np.mean at every n).
 __device__ __forceinline__ double pw_const_sum(int n, double v) {
   const int a0 = n >> 4;
   int K = 0, m = n;
@@ -681,8 +682,9 @@ __device__ __forceinline__ double run_leaf_value(double v, LeafCode lc, double s
 // seqsum values from the chain that also feeds the pair chain, so every lane runs the same
 // straight sequence -- one chain, two closed-form leaves, one ascent -- whatever its run's
 // shape (the leaf evaluations used to sit in three divergent branches, each with its own
-// chain).  tests/test_pw_const.py restates this line by line and checks it against numpy's
-// tree on explicit arrays.
+// chain).  tests/test_pw_const.py restates this line by line and checks that model against
+// numpy's tree on explicit arrays; the device code itself is checked by
+// tests/test_gpu_means.py (prefix, suffix and interior runs at every n, against np.mean).
 __device__ __forceinline__ double pw_run_sum(int n, int lo, int hi, double v) {
   lo = max(lo, 0);
   hi = min(hi, n);

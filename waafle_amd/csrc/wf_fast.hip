@@ -58,7 +58,8 @@ constexpr int kS0 = 640;          // ... and their score rows (potential clades 
 //   attachments:  hit[CAP] | sm[CAP] | abest[64] | ahit[64]      (annotations)
 //   means:        v[CAP] | runs | list[CAP] | rc[CAP]            (multi-run segments; the
 //                 level-0 pruning: segments to evaluate, clade-run sizes -- !FULL only)
-//   explain_one:  v | rank[CAP] (FULL; else in sc) | mem[CAP] | mx[64]
+//   explain_one:  v | rank[CAP] | mem[CAP] | mx[64] (FULL); v | mem[64] | mx[64] (else: ranks
+//                 in sc; past 64 options mem grows over mx, whose compact ranks are then unused)
 //   explain_two:  v | cl[CAP] | sib[CAP] | hm[CAP] | S[kS0] | masks, loci lists (FULL only)
 // key, lohi and sc (by attachment slot) live across roll-up levels.  Keys are 32-bit:
 // clade << 15 | locus << 9 | slot (clade ids < 2^17, checked on the host).
@@ -91,7 +92,11 @@ struct WaveSmem {
   __device__ uint8_t* rc() { return reinterpret_cast<uint8_t*>(scr + 8 * CAP + kRunsB + 2 * CAP); }  // !FULL
   __device__ double* rank() { return FULL ? reinterpret_cast<double*>(scr + 8 * CAP) : sc; }
   __device__ int* mem() { return reinterpret_cast<int*>(scr + (FULL ? 16 : 8) * CAP); }
-  __device__ unsigned long long* mx() { return reinterpret_cast<unsigned long long*>(scr + (FULL ? 20 : 12) * CAP); }
+  // (!FULL: right after mem's first 64 entries, inside the runs region, which is idle whenever
+  // mx is live -- the list compactions and explain_one.  At 12 * CAP it overlapped list for
+  // every CAP and rc for CAP 512: explain_one's option ranks overwrote the clade-run sizes
+  // it still had to read, and a contig's options past the 64th were lost.)
+  __device__ unsigned long long* mx() { return reinterpret_cast<unsigned long long*>(scr + (FULL ? 20 * CAP : 8 * CAP + 256)); }
   __device__ int* cl() { return reinterpret_cast<int*>(scr + 8 * CAP); }
   __device__ int* sib() { return reinterpret_cast<int*>(scr + 12 * CAP); }
   __device__ uint64_t* hm() { return reinterpret_cast<uint64_t*>(scr + 16 * CAP); }
@@ -103,6 +108,7 @@ struct WaveSmem {
   __device__ uint8_t* best_syn() { return reinterpret_cast<uint8_t*>(ign() + 192); }    // [64]
 };
 
+static_assert(256 + 64 * 8 <= WaveSmem<224, false>::kRunsB, "first form: mem[64] | mx[64] inside the runs region");
 static_assert(sizeof(WaveSmem<224, false>) <= 160 * 1024 / 16, "level-0 slice: 16 waves per CU");
 static_assert(sizeof(WaveSmem<256, true>) <= 160 * 1024 / 8, "FULL slice: 8 waves per CU");
 
