@@ -289,7 +289,12 @@ typedef struct wf_jn_result {   /* same residency as the batch */
   int64_t* coverage;          /* [sum(contig_length)] per-site coverage, contig-major, or NULL */
   int64_t* pair_first;        /* [n_pairs] first hit locus of each pair (-1: none), or NULL */
   uint64_t* pair_mask;        /* [n_pairs] bit i: locus pair_first + i hit (the pair's code
-                                 set, :277-286; WF_E_NOMEM if hits span more than 64 loci) */
+                                 set, :277-286).  The mask ends at locus pair_first + 63: a
+                                 pair may hit later loci of its contig too (always, at
+                                 min_overlap_sites <= 0); junction_hits and locus_hits
+                                 count those, and a caller that needs the whole set tests
+                                 loci pair_first + 64 .. loc_off[contig + 1] - 1 against the
+                                 two mates itself (waafle_amd/junctions.py: wide_hits) */
 } wf_jn_result;
 
 int wf_junctions(wf_ctx* ctx, const wf_jn_batch* batch, const wf_jn_params* params, wf_jn_result* out);

@@ -12,6 +12,10 @@ committed syn_small_* orgscorer fixtures).  For each case this runs, from /root/
     file in text mode, everything written is still the reference's own code);
   * `waafle_qc <lgt.tsv> <junctions.tsv> [--min-junction-hits N]` -> .qc_pass + stderr.
 
+The set `edges` is not seeded synthetic data but tests/junction_cases.py's edges_case(): the
+coverage, locus-geometry, hit-logic and wide-hit-set edge cases in one file set, run with the
+default --min-overlap-sites and with 0.  It has no .lgt.tsv, so waafle_qc is not run on it.
+
 The fixture `junc_<case>.json.gz` stores the recipe, flags and the reference's outputs.
 Run:  python tests/golden/make_junctions.py
 """
@@ -25,7 +29,9 @@ import tempfile
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.join(REPO, "tests"))
 from waafle_amd import synth, synth_reads  # noqa: E402
+import junction_cases  # noqa: E402
 
 RUNNER = r'''
 import gzip, sys
@@ -59,6 +65,8 @@ CASES = [
     # <= 0: every locus counts as hit (overlap 0 >= 0), including loci right of the pair
     ("small", ["--min-overlap-sites", "0"], []),
     ("short", ["--min-overlap-sites", "-3"], ["--min-junction-hits", "2"]),
+    ("edges", [], None),
+    ("edges", ["--min-overlap-sites", "0"], None),
 ]
 
 
@@ -72,17 +80,22 @@ def main(outdir=HERE):
     env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1", PYTHONHASHSEED="0")
     with tempfile.TemporaryDirectory() as tmp:
         for set_name, jflags, qflags in CASES:
-            gen, golden, reads = SETS[set_name]
             d = os.path.join(tmp, set_name)
             os.makedirs(d, exist_ok=True)
-            data = synth.generate(**gen)
-            fna, _, gff, _ = synth.write_text(data, d, "synth")
-            sam = synth_reads.write_sam(data, os.path.join(d, "reads.sam"), **reads)
-            with gzip.open(os.path.join(HERE, golden + ".json.gz"), "rt") as fh:
-                lgt_text = json.load(fh)["tsv"]["lgt"]
-            lgt = os.path.join(d, "synth.lgt.tsv")
-            with open(lgt, "w") as fh:
-                fh.write(lgt_text)
+            if set_name == "edges":
+                recipe = dict(cases="edges")
+                fna, gff, sam = junction_cases.by_name()["edges"].write_text(d, "synth")
+            else:
+                gen, golden, reads = SETS[set_name]
+                recipe = dict(generate=gen, reads=reads, lgt_golden=golden)
+                data = synth.generate(**gen)
+                fna, _, gff, _ = synth.write_text(data, d, "synth")
+                sam = synth_reads.write_sam(data, os.path.join(d, "reads.sam"), **reads)
+                with gzip.open(os.path.join(HERE, golden + ".json.gz"), "rt") as fh:
+                    lgt_text = json.load(fh)["tsv"]["lgt"]
+                lgt = os.path.join(d, "synth.lgt.tsv")
+                with open(lgt, "w") as fh:
+                    fh.write(lgt_text)
             out = os.path.join(d, "out_" + tag(jflags))
             os.makedirs(out, exist_ok=True)
             run = subprocess.run([sys.executable, "-c", RUNNER, fna, gff, "--sam", sam,
@@ -95,6 +108,15 @@ def main(outdir=HERE):
                     texts[ext] = fh.read()
             with gzip.open(os.path.join(out, "case.site_hits.tsv.gz"), "rt") as fh:
                 texts[".site_hits.tsv"] = fh.read()
+            if qflags is None:
+                name = "junc_{}_{}".format(set_name, tag(jflags))
+                fx = dict(case=name, recipe=recipe, junction_flags=jflags,
+                          junctions=texts[".junctions.tsv"], gene_hits=texts[".gene_hits.tsv"],
+                          site_hits=texts[".site_hits.tsv"])
+                with gzip.open(os.path.join(outdir, name + ".junc.json.gz"), "wt") as fh:
+                    json.dump(fx, fh, sort_keys=True)
+                print("{:50s} junction rows {:5d}".format(name, texts[".junctions.tsv"].count("\n") - 1))
+                continue
             qc_out = os.path.join(out, "case.qc_pass")
             qrun = subprocess.run([sys.executable, "-m", "waafle.waafle_qc", lgt,
                                    os.path.join(out, "case.junctions.tsv"), "--outfile",
@@ -105,7 +127,7 @@ def main(outdir=HERE):
                 with open(qc_out) as fh:
                     qc_text = fh.read()
             name = "junc_{}_{}_{}".format(set_name, tag(jflags), tag(qflags))
-            fx = dict(case=name, recipe=dict(generate=gen, reads=reads, lgt_golden=golden),
+            fx = dict(case=name, recipe=recipe,
                       junction_flags=jflags, qc_flags=qflags, junctions=texts[".junctions.tsv"],
                       gene_hits=texts[".gene_hits.tsv"], site_hits=texts[".site_hits.tsv"],
                       junctions_stderr=run.stderr, qc_returncode=qrun.returncode,

@@ -130,6 +130,11 @@ def materialize_junction(fixture, tmpdir):
     """(fna, gff, sam, lgt.tsv) paths for a junction fixture, rebuilt from its recipe."""
     from waafle_amd import synth, synth_reads
     r = fixture["recipe"]
+    if "cases" in r:                       # a set built by tests/junction_cases.py: no .lgt.tsv
+        import junction_cases
+        sub = os.path.join(str(tmpdir), "junc_" + r["cases"])
+        os.makedirs(sub, exist_ok=True)
+        return junction_cases.by_name()[r["cases"]].write_text(sub, "synth") + (None,)
     sub = os.path.join(str(tmpdir), "junc_" + "_".join(
         "{}{}".format(k, v) for k, v in sorted(r["generate"].items())))
     fna, gff = os.path.join(sub, "synth.fna"), os.path.join(sub, "synth.gff")

@@ -22,6 +22,7 @@ from waafle_amd import inputs, junctions, qc, synth, synth_reads
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = gc.junction_names()
+QC_NAMES = [n for n in NAMES if not n.startswith("junc_edges")]   # the edges set has no .lgt.tsv
 
 
 def min_sites(fx):
@@ -48,7 +49,7 @@ def test_oracle_matches_reference_junctions(name, tmp_path):
     assert gene == lines(fx["gene_hits"])
 
 
-@pytest.mark.parametrize("name", NAMES)
+@pytest.mark.parametrize("name", QC_NAMES)
 def test_oracle_and_product_qc_match_reference(name, tmp_path):
     fx = gc.load_junction(name)
     fna, gff, sam, lgt = gc.materialize_junction(fx, tmp_path)
@@ -65,7 +66,7 @@ def test_oracle_and_product_qc_match_reference(name, tmp_path):
     assert run.stderr == fx["qc_stderr"]
 
 
-@pytest.mark.parametrize("name", NAMES[:2])
+@pytest.mark.parametrize("name", QC_NAMES[:2])
 def test_product_readers_match_oracle(name, tmp_path):
     fx = gc.load_junction(name)
     fna, gff, sam, lgt = gc.materialize_junction(fx, tmp_path)

@@ -31,7 +31,7 @@ struct wf_ctx {
   // waafle_junctions staging and scratch
   DevBuf jn_site_off, jn_loc_off, jn_loc_contig, jn_lstart, jn_lend, jn_pc, jn_m1s, jn_m1e, jn_m2s, jn_m2e;
   DevBuf jn_diff, jn_cov, jn_prefix, jn_hits, jn_lhits, jn_c1, jn_c2, jn_cj, jn_ratio, jn_tmp;
-  DevBuf jn_pfirst, jn_pmask, jn_ovf;
+  DevBuf jn_pfirst, jn_pmask;
   bool have_lin = false;
   int64_t lds_bytes = 24 * 1024;   // decision arena per workgroup (wf_set_lds_bytes)
   // staging for host-resident batches
@@ -218,7 +218,7 @@ void wf_free(wf_ctx* ctx) {
                     &ctx->jn_lend, &ctx->jn_pc, &ctx->jn_m1s, &ctx->jn_m1e, &ctx->jn_m2s,
                     &ctx->jn_m2e, &ctx->jn_diff, &ctx->jn_cov, &ctx->jn_prefix, &ctx->jn_hits,
                     &ctx->jn_lhits, &ctx->jn_c1, &ctx->jn_c2, &ctx->jn_cj, &ctx->jn_ratio,
-                    &ctx->jn_tmp, &ctx->jn_pfirst, &ctx->jn_pmask, &ctx->jn_ovf,
+                    &ctx->jn_tmp, &ctx->jn_pfirst, &ctx->jn_pmask,
                     &ctx->b_hit_off, &ctx->b_qlo, &ctx->b_qhi, &ctx->b_taxon, &ctx->b_hstrand,
                     &ctx->b_score, &ctx->b_scov, &ctx->b_sysmask, &ctx->b_hkey, &ctx->b_loc_off,
                     &ctx->b_lstart, &ctx->b_lend, &ctx->b_lstrand, &ctx->r_call, &ctx->r_crit,
@@ -655,8 +655,7 @@ int wf_junctions(wf_ctx* ctx, const wf_jn_batch* b, const wf_jn_params* p, wf_jn
   if (r->pair_first || r->pair_mask) {
     if (!r->pair_first || !r->pair_mask) return fail(ctx, WF_E_BADINPUT, "pair_first and pair_mask go together");
     if ((rc = alloc_out(ctx, ctx->jn_pfirst, NP, &a.pair_first)) ||
-        (rc = alloc_out(ctx, ctx->jn_pmask, NP, &a.pair_mask)) ||
-        (rc = alloc_out(ctx, ctx->jn_ovf, 1, &a.overflow)))
+        (rc = alloc_out(ctx, ctx->jn_pmask, NP, &a.pair_mask)))
       return rc;
   }
   const size_t tb = wf::junctions_tmp_bytes(S);
@@ -671,10 +670,8 @@ int wf_junctions(wf_ctx* ctx, const wf_jn_batch* b, const wf_jn_params* p, wf_jn
       (rc = download(ctx, r->ratio, a.ratio, NL)))
     return rc;
   if (r->locus_hits && (rc = download(ctx, r->locus_hits, a.locus_hits, NL))) return rc;
-  unsigned overflow = 0;
   if (a.pair_first && ((rc = download(ctx, r->pair_first, a.pair_first, NP)) ||
-                       (rc = download(ctx, r->pair_mask, a.pair_mask, NP)) ||
-                       (rc = download(ctx, &overflow, a.overflow, 1))))
+                       (rc = download(ctx, r->pair_mask, a.pair_mask, NP))))
     return rc;
   if (r->coverage) {   // drop the sentinel slot of each contig
     for (int64_t c = 0; c < N; ++c) {
@@ -683,8 +680,6 @@ int wf_junctions(wf_ctx* ctx, const wf_jn_batch* b, const wf_jn_params* p, wf_jn
     }
   }
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  if (overflow)
-    return fail(ctx, WF_E_NOMEM, "%u read pairs hit loci more than 64 apart (pair_mask holds 64)", overflow);
   return WF_OK;
 }
 

@@ -161,7 +161,6 @@ struct JnArgs {
   int32_t* locus_hits;                     // [n_loci] pairs hitting locus j, or null
   int64_t* pair_first;                     // [n_pairs] first hit locus (-1: none), or null
   uint64_t* pair_mask;                     // [n_pairs] hit loci first .. first + 63
-  unsigned* overflow;                      // pairs with a hit 64+ loci after their first
   double* cov1; double* cov2; double* covj; double* ratio;   // [n_loci] per junction j
 };
 int junctions_run(const JnArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s, std::string* err);

@@ -70,8 +70,8 @@ __global__ void k_jn_cover(const JnArgs A) {
     if (hit && A.locus_hits) atomicAdd(&A.locus_hits[k], 1);
     if (hit) {                                   // the pair's hit set (gene-pair hits)
       if (first < 0) first = k;
-      if (k - first < 64) mask |= 1ull << (k - first);
-      else if (A.pair_first) atomicAdd(A.overflow, 1u);
+      if (k - first < 64) mask |= 1ull << (k - first);   // later hits: the caller's, from
+                                                         // the coordinates (wf_jn_result)
     }
     prev = hit;
   }
@@ -123,7 +123,6 @@ int junctions_run(const JnArgs& a, void* tmp, size_t tmp_bytes, hipStream_t s, s
   JN_TRY(hipMemsetAsync(a.junction_hits, 0, (size_t)std::max<int64_t>(a.n_loci, 1) * sizeof(int32_t), s));
   if (a.locus_hits)
     JN_TRY(hipMemsetAsync(a.locus_hits, 0, (size_t)std::max<int64_t>(a.n_loci, 1) * sizeof(int32_t), s));
-  if (a.pair_first) JN_TRY(hipMemsetAsync(a.overflow, 0, sizeof(unsigned), s));
   if (a.n_pairs > 0)
     hipLaunchKernelGGL(k_jn_cover, dim3((unsigned)((a.n_pairs + 255) / 256)), dim3(256), 0, s, a);
   JN_TRY(hipGetLastError());

@@ -65,9 +65,18 @@ def read_groups(path):
             np.ascontiguousarray(scov, dtype=np.float64))
 
 
-def call_genes(path, min_overlap=0.1, min_gene_length=200.0, min_scov=0.75, device=0):
-    names, off, qs, qe, strand, scov = read_groups(path)
-    G, NH = len(names), int(off[-1])
+def call_genes_arrays(off, qstart, qend, strand, scov, min_overlap=0.1, min_gene_length=200.0,
+                      min_scov=0.75, device=0):
+    """wf_genecall on host arrays: `off` int64[G + 1] hit range of each group, per hit
+    `qstart`/`qend` int32, `strand` int8 (1: minus) and `scov` float64.  Returns
+    (n_genes int32[G], gene_start, gene_stop int32[n_hits], gene_strand int8[n_hits]); group
+    g's genes lie at off[g] .. off[g] + n_genes[g]."""
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    qs = np.ascontiguousarray(qstart, dtype=np.int32)
+    qe = np.ascontiguousarray(qend, dtype=np.int32)
+    strand = np.ascontiguousarray(strand, dtype=np.int8)
+    scov = np.ascontiguousarray(scov, dtype=np.float64)
+    G, NH = len(off) - 1, int(off[-1])
     n_genes = np.zeros(max(G, 1), dtype=np.int32)
     gs = np.zeros(max(NH, 1), dtype=np.int32)
     ge = np.zeros(max(NH, 1), dtype=np.int32)
@@ -90,8 +99,15 @@ def call_genes(path, min_overlap=0.1, min_gene_length=200.0, min_scov=0.75, devi
             raise L.WaafleHipError(rc, so.wf_last_error(h).decode())
     finally:
         so.wf_free(h)
+    return n_genes[:G], gs[:NH], ge[:NH], gst[:NH]
+
+
+def call_genes(path, min_overlap=0.1, min_gene_length=200.0, min_scov=0.75, device=0):
+    names, off, qs, qe, strand, scov = read_groups(path)
+    n_genes, gs, ge, gst = call_genes_arrays(off, qs, qe, strand, scov, min_overlap,
+                                             min_gene_length, min_scov, device)
     genes = []
-    for g in range(G):
+    for g in range(len(names)):
         o = int(off[g])
         k = int(n_genes[g])
         genes.append([(int(gs[o + i]), int(ge[o + i]), "-" if gst[o + i] else "+")

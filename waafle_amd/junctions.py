@@ -178,9 +178,52 @@ def score_junctions(table, pairs, min_overlap_sites=25, device=0, coverage=False
         rc = so.wf_junctions(h, C.byref(b), C.byref(p), C.byref(r))
         if rc != L.WF_OK:
             raise L.WaafleHipError(rc, so.wf_last_error(h).decode())
+        if pair_sets:
+            out["wide_pair"], out["wide_locus"] = wide_hits(
+                table, (pc, m1s, m1e, m2s, m2e), out["pair_first"], int(min_overlap_sites))
         return out
     finally:
         so.wf_free(h)
+
+
+def _overlap_sites(a1, a2, b1, b2):
+    """utils.calc_overlap(normalize=False) (utils.py:487-500) on broadcast int64 arrays."""
+    a1, a2 = np.minimum(a1, a2), np.maximum(a1, a2)
+    b1, b2 = np.minimum(b1, b2), np.maximum(b1, b2)
+    ov = np.minimum(a2, b2) - np.maximum(a1, b1) + 1
+    return np.where((b1 > a2) | (a1 > b2), 0, ov)
+
+
+def wide_hits(table, pairs, first, min_overlap_sites, chunk=2048):
+    """The hit loci that pair_mask has no bit for: (pair, locus) index arrays of every hit at
+    locus pair_first + 64 or later.  Only a pair whose contig has loci that far past its
+    first hit can have one; those pairs are tested against those loci here, on the host, with
+    find_hit_loci's rule (:277-286), one contig at a time.  Memory: a few temporaries of
+    chunk x (loci past first + 64) int64 per step, 16 KiB per locus at the default chunk."""
+    pc = np.asarray(pairs[0], dtype=np.int64)
+    first = np.asarray(first, dtype=np.int64)
+    m1s, m1e, m2s, m2e = [np.asarray(a, dtype=np.int64) for a in pairs[1:5]]
+    cand = np.nonzero((first >= 0) & (table.loc_off[pc + 1] > first + 64))[0]
+    if min_overlap_sites > 0 and len(cand) and bool((table.loc_start <= table.loc_end).all()):
+        # loci are sorted by start: one that starts past the pair's right end misses, and so
+        # does every later one (the kernel's early exit)
+        rmax = np.maximum(np.maximum(m1s, m1e), np.maximum(m2s, m2e))
+        cand = cand[table.loc_start[first[cand] + 64] <= rmax[cand]]
+    out_p, out_k = [np.zeros(0, np.int64)], [np.zeros(0, np.int64)]
+    for c in np.unique(pc[cand]).tolist():
+        l1 = int(table.loc_off[c + 1])
+        sel = cand[pc[cand] == c]
+        for i in range(0, len(sel), chunk):
+            p = sel[i:i + chunk]
+            k = np.arange(int(first[p].min()) + 64, l1, dtype=np.int64)
+            a1, a2 = table.loc_start[k][None, :], table.loc_end[k][None, :]
+            hit = (_overlap_sites(a1, a2, m1s[p][:, None], m1e[p][:, None]) >= min_overlap_sites) | \
+                  (_overlap_sites(a1, a2, m2s[p][:, None], m2e[p][:, None]) >= min_overlap_sites)
+            hit &= k[None, :] >= first[p][:, None] + 64
+            pi, ki = np.nonzero(hit)
+            out_p.append(p[pi])
+            out_k.append(k[ki])
+    return np.concatenate(out_p), np.concatenate(out_k)
 
 
 # ---------------------------------------------------------------------------
@@ -227,7 +270,9 @@ def gene_hit_rows(table, pairs, res):
     """write_detailed_output gene-pair hits (:347-371) from the device's per-pair hit sets:
     per contig with >= 1 concordant pair, every stored (code1, code2) key with
     code2 <= code1, sorted.  A pair adds 1 to (x, x) for each code x it hits and to (x, y)
-    for each ordered pair of distinct codes (:437-451)."""
+    for each ordered pair of distinct codes (:437-451).  res: pair_first and pair_mask of
+    wf_junctions, plus wide_pair / wide_locus (wide_hits) when a pair can hit loci past the
+    mask, as score_junctions(pair_sets=True) returns them."""
     lines = ["\t".join(f.upper() for f in GENE_FIELDS)]
     pc = np.asarray(pairs[0], dtype=np.int64)
     first, mask = res["pair_first"], res["pair_mask"]
@@ -241,6 +286,9 @@ def gene_hit_rows(table, pairs, res):
         idx = np.nonzero(sel)[0]
         pp.append(idx)
         cc.append(loc_code[first[idx] + bit])
+    if "wide_pair" in res:                        # hits past the mask's 64 loci (wide_hits);
+        pp.append(res["wide_pair"])               # absent: no pair hits that far
+        cc.append(loc_code[res["wide_locus"]])
     P = np.concatenate(pp).astype(np.int64)
     K = np.concatenate(cc).astype(np.int64)
     ncode = max(len(codes), 1)
