@@ -480,6 +480,56 @@ constexpr int kE2Seg = 320;        // segments of one compact table (LDS of k_du
 constexpr int kE2MaxG = 63;        // loci (locus masks keep bit 63 for the root flag)
 constexpr int kPruneMax = 64;      // attachments scanned for whole-locus domination
 
+// Bounds of a segment's mean from its envelope's integral (the first wave form's pruning).
+// Site x of the segment holds max(0, max{score_a : lo_a <= x < hi_a}); the mean is numpy's
+// pairwise sum of those sites over len.  env_integral sweeps the sites left to right by one
+// lane: each turn finds the envelope's value at p and the next site nx at which an attachment
+// starts or ends, and adds value * (nx - p) -- at most 2 * na + 1 turns of na attachments
+// each, no leaf table, no site array.  I = sum / len in plain double; every term is >= 0, so
+// I's relative error is at most (turns + 2) * 2^-53 < 2e-14 for na <= kPruneMax, and numpy's
+// tree over <= 8191 non-negative sites is within 1e-14 of the real mean: the exact mean lies
+// in [I (1 - 2e-12), I (1 + 2e-12)] with two orders of magnitude to spare.  `best` gets the
+// envelope's maximum, the best score among the attachments that cover a site (another upper
+// bound).  range(q, lo, hi), score(q): attachment q.
+constexpr double kEnvSlack = 2e-12;
+template <class Rg, class Sc>
+__device__ __forceinline__ double env_integral(Rg range, Sc score, int kb, int ke, int len, double& best) {
+  double acc = 0.0;
+  best = 0.0;
+  for (int p = 0; p < len;) {
+    int nx = len;
+    double val = 0.0;
+    for (int q = kb; q < ke; ++q) {
+      int l, h;
+      range(q, l, h);
+      if (l >= h) continue;                          // an empty range covers nothing
+      if (l <= p && p < h) {
+        const double s = score(q);                   // (read only where the range covers p)
+        val = s > val ? s : val;
+        nx = h < nx ? h : nx;
+      } else if (l > p) {
+        nx = l < nx ? l : nx;
+      }
+    }
+    best = val > best ? val : best;
+    acc += val * (double)(nx - p);
+    p = nx;
+  }
+  return acc / (double)len;
+}
+// The not-evaluated marker of a first-form segment is v = -1 - ub (ub: its upper bound).  For
+// a segment whose ub is tight -- one attachment: score x share x (1 + slack); 2..kPruneMax:
+// min(best score, I (1 + slack)) -- the marker also yields a lower bound.  ub <= I' (1 +
+// 2e-12) with I' the integral (or score x share), so ub (1 - 5e-12) <= I' (1 - 2.9e-12) <=
+// mean; -1 - ub rounds by at most half an ulp of 1 + ub (and -1 - v is then exact), which the
+// absolute term covers twice over.
+__device__ __forceinline__ double marker_ub(double v) { return -1.0 - v; }
+__device__ __forceinline__ double marker_lb(double v) {
+  const double ub = -1.0 - v;
+  const double lb = ub * (1.0 - 5e-12) - 4.5e-16 * (1.0 + ub);
+  return lb > 0.0 ? lb : 0.0;
+}
+
 __device__ __forceinline__ bool attaches(const DevParams& P, int qlo, int qhi, int hs, int l1,
                                          int len, int lst) {
   if (P.stranded && hs != lst) return false;

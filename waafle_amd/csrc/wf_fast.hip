@@ -900,6 +900,12 @@ __global__ __launch_bounds__(64, FULL ? 2 : (ROLL ? kRollWaves : 4)) void k_wave
     // the roll-up attachments in descending-score order for early exits saved what its extra
     // sort cost, r4j, and was removed.)
     constexpr bool kKeyOrder = !FULL && !ROLL;
+    // Envelope-integral bounds of multi-attachment segments and explain_one from intervals
+    // (the prune set-up below): the roll-up launches only.  At level 0 the triage leaves the
+    // first form the explain_two contigs, which have no option to rank and few multi-run
+    // segments: there the sweep and the interval walk cost 0.1 ms and saved nothing (r8).
+    constexpr bool kEnvOn = ROLL;
+    constexpr bool kIvOn = ROLL;
     using Src = typename std::conditional<kKeyOrder, SliceSrcKey, SliceSrc>::type;
     auto slot_at = [&](int t) -> int { return kKeyOrder ? (int)(F.key[t] & kSlotMask) : t; };
     for (int level = start_level; !staged && G > 0 && h1 > h0; ++level) {   // else: never evaluated (:959)
@@ -1002,6 +1008,22 @@ __global__ __launch_bounds__(64, FULL ? 2 : (ROLL ? kRollWaves : 4)) void k_wave
           const int run = max(0, hi16(x) - lo16(x));
           return fmin(sc, sc * ((double)run / (double)len) * (1.0 + 2e-12));
         }
+        if (kEnvOn && ke - kb <= kPruneMax) {
+          // several attachments (first form): the envelope's integral, one sweep by this lane
+          // (env_integral, wf_device.h) -- tight where the best score is loose by the part of
+          // the locus a partial hit leaves to the others
+          double best;
+          const double I = env_integral(
+              [&](int q, int& l, int& h) {
+                const uint32_t x = F.lohi[slot_at(q)];
+                l = lo16(x); h = hi16(x);
+              },
+              [&](int q) -> double { return F.sc[slot_at(q)]; },
+              kb, ke, F.len[cg_of(F, t).y], best);
+          // (numpy's rounded mean of a locus the best hit covers whole can exceed that score
+          // by an ulp or two: the cap carries the tree's rounding)
+          return fmin(best * (1.0 + 1e-14), I * (1.0 + kEnvSlack));
+        }
         for (int q = kb; q < ke; ++q) ub = fmax(ub, F.sc[slot_at(q)]);
         return ub;
       };
@@ -1015,8 +1037,12 @@ __global__ __launch_bounds__(64, FULL ? 2 : (ROLL ? kRollWaves : 4)) void k_wave
       // and potential flag count it, a member's row evaluates it in pass 5, and otherwise the
       // table carries lb_thr in its place (the same answer to every such comparison).
       const double lb_thr = fmax(fmax(P.k2, P.sister_on ? P.sister_thr : 0.0), P.kmin);
+      // (callers: first form, v[t] < 0.  ROLL: up to kPruneMax attachments the marker's bound
+      // is tight -- one run's share, or the envelope's integral -- and gives the lower bound
+      // too; beyond, and at level 0, the best score x share as before.)
       auto lb_mean = [&](int t) -> double {
         const int kb = seg_first(F, t), ke = t + 1 < ns ? seg_first(F, t + 1) : n_att;
+        if (kEnvOn && ke - kb <= kPruneMax) return marker_lb(v[t]);
         const double len = (double)F.len[cg_of(F, t).y];
         double lb = 0.0;
         for (int q = kb; q < ke; ++q) {
@@ -1079,13 +1105,63 @@ __global__ __launch_bounds__(64, FULL ? 2 : (ROLL ? kRollWaves : 4)) void k_wave
             rc[t] = (uint8_t)rsz[i];
           }
         }
+        if (kIvOn) wave_sync();                       // (the walk reads other lanes' v and rc)
+        // explain_one from intervals (first form, under lb_um's conditions, --range >= 0).
+        // When the bounds alone unmask every locus, um is all loci whatever pass 0 evaluates,
+        // and the options are the clades on every locus.  Each such clade's crit lies in
+        // [min lb, min ub] and its rank in [sum lb, sum ub] / G (a sum of <= 64 non-negative
+        // terms in any order: 1e-12 covers it).  A clade is evaluated unless its crit cannot
+        // reach k1, or its rank cannot come within --range of the best rank lower bound among
+        // the clades that are surely options: then it is neither the best option nor in the
+        // meld list.  Its run size becomes 0, so neither pass 0 nor explain_one sees it; later
+        // passes treat its segments like any other segment not evaluated.  Two ranks the
+        // bounds cannot order are both kept, so every comparison that decides (`better`, the
+        // meld range, ties by clade id) is made on exact values.
+        if (kIvOn && lb_um && P.range >= 0.0 && lb_um_bits(allG) == allG) {
+          double best_lb = -__builtin_inf();          // first walk: the best sure option's rank
+#pragma unroll 1
+          for (int t0 = 0; t0 < ns; t0 += 64) {
+            const int t = t0 + lane;
+            const bool head = t < ns && (int)rc[t] == G &&
+                              (t == 0 || (F.seg[t - 1] >> kCladeShift) != (F.seg[t] >> kCladeShift));
+            if (head) {
+              double cl = __builtin_inf(), sl = 0.0;
+              for (int q = t; q < t + G; ++q) {
+                const double l = lb_mean(q);
+                cl = fmin(cl, l);
+                sl += l;
+              }
+              if (cl >= P.k1 * (1.0 + 1e-12)) best_lb = fmax(best_lb, sl / (double)G * (1.0 - 1e-12));
+            }
+          }
+          best_lb = wave_butterfly(best_lb, [](double a, double b) { return b > a ? b : a; });
+          const double need = (best_lb - P.range) - 1e-11 * (1.0 + fabs(best_lb) + P.range);
+#pragma unroll 1
+          for (int t0 = 0; t0 < ns; t0 += 64) {
+            const int t = t0 + lane;
+            const bool head = t < ns && (int)rc[t] == G &&
+                              (t == 0 || (F.seg[t - 1] >> kCladeShift) != (F.seg[t] >> kCladeShift));
+            if (head) {
+              double cu = __builtin_inf(), su = 0.0;
+              for (int q = t; q < t + G; ++q) {
+                const double u = marker_ub(v[q]);
+                cu = fmin(cu, u);
+                su += u;
+              }
+              const bool keep = cu >= P.k1 * (1.0 - 1e-12) && su / (double)G * (1.0 + 1e-12) >= need;
+              if (!keep)
+                for (int q = t; q < t + G; ++q) rc[q] = 0;
+            }
+          }
+          wave_sync();
+        }
         // pass 0's list (segments of clades on every locus), in segment order
         uint16_t* lst = F.list();
         n_pass0 = 0;
 #pragma unroll
         for (int i = 0; i < kCh; ++i) {
           const int t = 64 * i + lane;
-          const bool in = t < ns && rsz[i] == G;
+          const bool in = t < ns && (kIvOn ? (int)rc[t] : rsz[i]) == G;   // (rc: the walk's drops)
           const uint64_t im = __ballot(in);
           if (in) lst[n_pass0 + __popcll(im & lanes_below())] = (uint16_t)t;
           n_pass0 += __popcll(im);
