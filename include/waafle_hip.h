@@ -157,7 +157,8 @@ typedef struct wf_batch {
      hit's filter fields packed in one word, wf_pack_hit_keys' layout -- bits 0-23 hit_taxon,
      bit 24 hit_scov >= params.min_scov (the attach_hits filter, orgscorer.py:363-364: it
      must be packed with the min_scov of the wf_score call it is passed to), bit 25
-     hit_strand '-', bits 26-31 hit_sysmask & 63 (systems 0-5).  The level-0 triage, the
+     hit_strand '-', bits 26-31 hit_sysmask & 63 (systems 0-5; also when n_systems is 0, from
+     the library's own packer too).  The level-0 triage, the
      kernel of most contigs, then reads 20 bytes per hit (qlo, qhi, key, score) instead of
      32.  The other arrays stay required (the other kernels read them). */
   const uint32_t* hit_key;    /* [n_hits] */

@@ -50,13 +50,15 @@ def load(name):
         return json.load(fh)
 
 
-def demo_file(fname, tmpdir):
-    dest = os.path.join(str(tmpdir), fname)
+def unpack(src_gz, dest):
     if not os.path.exists(dest):
-        with gzip.open(os.path.join(GOLDEN, "demo_inputs", fname + ".gz"), "rb") as src, \
-                open(dest, "wb") as out:
+        with gzip.open(src_gz, "rb") as src, open(dest, "wb") as out:
             shutil.copyfileobj(src, out)
     return dest
+
+
+def demo_file(fname, tmpdir):
+    return unpack(os.path.join(GOLDEN, "demo_inputs", fname + ".gz"), os.path.join(str(tmpdir), fname))
 
 
 def materialize(fixture, tmpdir):
@@ -67,8 +69,10 @@ def materialize(fixture, tmpdir):
     if recipe["kind"] == "files":
         d = os.path.join(GOLDEN, recipe["dir"])
         stem = recipe.get("stem", "tie")
-        return [os.path.join(d, stem + e) for e in
-                (".fna", ".blastout", ".gff", ".taxonomy.tsv")]
+        names = [stem + e for e in (".fna", ".blastout", ".gff", ".taxonomy.tsv")]
+        if recipe.get("gz"):               # committed gzipped: unpacked once per directory
+            return [unpack(os.path.join(d, n + ".gz"), os.path.join(str(tmpdir), n)) for n in names]
+        return [os.path.join(d, n) for n in names]
     from waafle_amd import synth
     sub = os.path.join(str(tmpdir), "synth_" + "_".join(
         "{}{}".format(k, v) for k, v in sorted(recipe["params"].items())))

@@ -298,6 +298,27 @@ def test_wave_levels_decline_after_a_raise(scorer, tmp_path):
         assert ph["rollup"][1] > 0 and ph["attach"][1] > 0, ph
 
 
+def test_attach_fixture_reaches_the_staged_attach(tmp_path):
+    """The default `attach` fixture (make_attach.py) in the default form: its 513-hit contig is
+    past every wave slice, so the counting kernel sends it to the staged kernels and their
+    attach phase runs; the records equal the oracle's."""
+    fx = gc.load("attach_default")
+    paths = gc.materialize(fx, tmp_path)
+    batch, tax = inputs.load_inputs(*paths, 200.0, warn=None)
+    assert int(np.diff(batch.hit_off).max()) == 513
+    s = engine.GpuScorer(0, **FORMS["level0"])
+    tm = lib.WfTiming()
+    s.lib.wf_timing_enable(s.h, 1)
+    try:
+        got = gpu_score(s, batch, tax, fx["flags"])
+        assert s.lib.wf_timing_read(s.h, C.byref(tm)) == 0
+    finally:
+        s.close()
+    assert_same_results(got, oracle_for(("golden", "attach_default"), paths, fx["flags"], batch, tax), batch)
+    ph = tm.phases()
+    assert ph["attach"][1] > 0 and ph["segments"][1] > 0, ph
+
+
 def test_full_size_cfg2_properties():
     """BASELINE config 2 at full size: deterministic, shard-invariant, LDS-budget
     invariant (forcing the HBM-workspace kernel), equal across every execution form, and

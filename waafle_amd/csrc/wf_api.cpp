@@ -379,8 +379,8 @@ static int check_batch(wf_ctx* ctx, const wf_batch* b, const wf_params* p, const
     if (b->hit_key)                // the packed words must say what the arrays say
       for (int64_t i = 0; i < b->n_hits; ++i) {
         const uint32_t k = b->hit_key[i];
-        const uint32_t want = (uint32_t)b->hit_taxon[i] | (uint32_t)(b->hit_scov[i] >= p->min_scov) << 24 |
-                              (uint32_t)(b->hit_strand[i] == 1) << 25 | (b->hit_sysmask[i] & 63u) << 26;
+        const uint32_t want = wf::pack_hit_key(b->hit_taxon[i], b->hit_scov[i] >= p->min_scov, b->hit_strand[i] == 1,
+                                               b->hit_sysmask[i]);
         if (k != want)
           return fail(ctx, WF_E_BADINPUT, "hit %lld: hit_key 0x%08x, its arrays (min_scov %g) give 0x%08x",
                       (long long)i, k, p->min_scov, want);
@@ -503,8 +503,7 @@ int wf_pack_hit_keys(int64_t n_hits, const int32_t* taxon, const int8_t* strand,
   if (n_hits < 0 || (n_hits > 0 && (!taxon || !strand || !scov || !sysmask || !out))) return WF_E_BADINPUT;
   for (int64_t i = 0; i < n_hits; ++i) {
     if (taxon[i] < 0 || taxon[i] >= (1 << 24) || (strand[i] != 0 && strand[i] != 1)) return WF_E_BADINPUT;
-    out[i] = (uint32_t)taxon[i] | (uint32_t)(scov[i] >= min_scov) << 24 | (uint32_t)(strand[i] == 1) << 25 |
-             (sysmask[i] & 63u) << 26;
+    out[i] = wf::pack_hit_key(taxon[i], scov[i] >= min_scov, strand[i] == 1, sysmask[i]);
   }
   return WF_OK;
 }

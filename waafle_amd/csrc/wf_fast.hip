@@ -28,7 +28,7 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "wf_device.h"
+#include "wf_attach.h"
 #include "wf_lanes.h"
 
 namespace wf {
@@ -45,7 +45,6 @@ constexpr int kRuns0 = 64;           // envelope runs of a multi-attachment segm
 constexpr int kMultiAtt0 = 32;       // ... so at most 32 attachments (2 * 32 - 1 runs);
 constexpr int kRunsL0 = 32;          // the level-0 form: 16 attachments (a 10 KB slice:
 constexpr int kMultiAttL0 = 16;      // 16 waves per CU, see WaveSmem)
-constexpr int kXcds = 8;             // MI355X: 8 XCDs of 32 CUs, each with its own L2
 // resident waves per SIMD of the roll-up launches: 4 (128 VGPRs, some spilled) beat 3 (168,
 // none) by 0.35 ms of roll-up per cfg4 pass on one box (r4f: their few contigs per wave
 // want occupancy more than registers; again r5u: 3 waves +0.45 ms)
@@ -111,11 +110,6 @@ struct WaveSmem {
 static_assert(256 + 64 * 8 <= WaveSmem<224, false>::kRunsB, "first form: mem[64] | mx[64] inside the runs region");
 static_assert(sizeof(WaveSmem<224, false>) <= 160 * 1024 / 16, "level-0 slice: 16 waves per CU");
 static_assert(sizeof(WaveSmem<256, true>) <= 160 * 1024 / 8, "FULL slice: 8 waves per CU");
-
-__device__ __forceinline__ int leaves_for(const SArgs& S, int len) {
-  return (len / kNpyBuf) * (S.lut_off[kNpyBuf + 1] - S.lut_off[kNpyBuf]) +
-         (S.lut_off[len % kNpyBuf + 1] - S.lut_off[len % kNpyBuf]);
-}
 
 __device__ __forceinline__ uint64_t lanes_below() { return (1ull << lane_id()) - 1ull; }
 
@@ -675,13 +669,7 @@ __global__ __launch_bounds__(64, FULL ? 2 : (ROLL ? kRollWaves : 4)) void k_wave
   extern __shared__ __attribute__((aligned(16))) char smem[];
   WaveSmem<CAP, FULL>& F = *reinterpret_cast<WaveSmem<CAP, FULL>*>(smem);
   const int lane = threadIdx.x;
-  // XCD-aware contig order.  Workgroups are dealt to the 8 XCDs round-robin (blockIdx % 8),
-  // so a plain grid stride puts neighbouring contigs on different XCDs, and the record
-  // fields of 8 neighbours (1-8 B each, one array per field) share cache lines that 8 L2s
-  // write back partially.  Instead XCD x's j-th workgroup takes contig (8 k + x) * B + j at
-  // step k (B = grid / 8): each XCD walks runs of B consecutive contigs.
-  const bool xmap = gridDim.x % kXcds == 0;
-  const int xb = (int)gridDim.x / kXcds, xj = (int)blockIdx.x / kXcds, xx = (int)blockIdx.x % kXcds;
+  const XcdOrder order = xcd_order();               // (the static order, without a queue)
   for (int it = 0;; ++it) {
     int ci;
     if (S_arg.wq) {
@@ -692,7 +680,7 @@ __global__ __launch_bounds__(64, FULL ? 2 : (ROLL ? kRollWaves : 4)) void k_wave
       if (lane == 0) q = atomicAdd(S_arg.wq, 1ull);
       ci = __builtin_amdgcn_readfirstlane((int)q);
     } else {
-      ci = xmap ? (it * kXcds + xx) * xb + xj : (int)blockIdx.x + it * (int)gridDim.x;
+      ci = order.at(it);
     }
     if (ci >= n_list) break;
     const int c = list ? list[ci] : ci;
@@ -739,25 +727,19 @@ __global__ __launch_bounds__(64, FULL ? 2 : (ROLL ? kRollWaves : 4)) void k_wave
     const int Gs = min(G, kLoc0);
     // ---- loci (lane g), leaf-table bases ----
     int nl1 = 0;
-    int my_lo = 0, my_hi = -1;
+    Locus my{0, -1, 0};
     if (lane < Gs) {
-      const int a = K.lstart[l0 + lane], b = K.lend[l0 + lane];
-      const int len = max(a, b) - min(a, b) + 1;
-      my_lo = min(a, b);
-      my_hi = max(a, b);
-      F.lo[lane] = my_lo;
+      my = load_locus(K, l0 + lane);
+      const int len = my.len();
+      F.lo[lane] = my.lo;
       F.len[lane] = len;
-      F.st[lane] = K.lstrand[l0 + lane];
+      F.st[lane] = my.st;
       if (len < kNpyBuf) nl1 = S.lut_off[len + 1] - S.lut_off[len];
       F.nl1[lane] = (int16_t)nl1;
     }
-    // loci ascending and disjoint (the usual GFF): with min_overlap > 0 a hit attaches only
-    // to the loci it overlaps (a disjoint pair scores 0 < min_overlap), which are a run found
-    // by binary search -- the attach loop then visits those, in GFF order, instead of every
-    // locus per hit
-    const int prev_hi = __shfl_up(my_hi, 1, 64);
-    const bool ordered = G <= kLoc0 && P.min_overlap > 0.0 &&
-                         __ballot(lane >= 1 && lane < Gs && my_lo <= prev_hi) == 0ull;
+    // the attach loop visits the loci a hit overlaps, not every locus per hit (wf_attach.h)
+    const bool loci_ordered = wave_loci_ordered(lane, Gs, my.lo, my.hi);
+    const bool ordered = G <= kLoc0 && P.min_overlap > 0.0 && loci_ordered;
     int lut_total;
     const int lb = wave_excl_scan(nl1, &lut_total);
     F.lbase[lane] = (int16_t)min(lb, 32767);
@@ -783,6 +765,9 @@ __global__ __launch_bounds__(64, FULL ? 2 : (ROLL ? kRollWaves : 4)) void k_wave
 
     WLAP(0);
     // ---- hits -> attachments, in (hit, locus) order (orgscorer.py:359-382) ----
+    const LociByLen V{F.lo, F.len, F.st};
+    // (the loci past the slice's kLoc0 are counted only: the contig goes staged)
+    const LociOrBatch Vall{V, K, l0, kLoc0};
     int n_att = 0;
     long long nl_sum = 0;
     // kHB batches of 64 hits per round: every field of all of them is loaded up front (one
@@ -806,37 +791,21 @@ __global__ __launch_bounds__(64, FULL ? 2 : (ROLL ? kRollWaves : 4)) void k_wave
           scv = r_scv[b]; sc = r_sc[b]; m = r_m[b];
         }
       if (ordered && h < h1 && scv >= P.min_scov) {
-        int g = 0;                                   // first locus ending at or after qlo
-#pragma unroll
-        for (int k = 32; k > 0; k >>= 1) {
-          const int i = min(g + k, Gs) - 1;
-          if (g + k <= Gs && F.lo[i] + F.len[i] - 1 < qlo) g += k;
-        }
-        for (; g < Gs; ++g) {
-          const int lo = F.lo[g], len = F.len[g];
-          if (lo > qhi) break;
-          if (attaches(P, qlo, qhi, hs, lo, len, F.st[g])) {
-            ++n;
-            nl_sum += len < kNpyBuf ? F.nl1[g] : leaves_for(S, len);
-            am |= 1ull << g;
-          }
-        }
+        const int g0 = first_locus<kLoc0>(Gs, qlo, [&](int g) { return V.hi(g); });
+        each_attached<true>(P, V, g0, Gs, qlo, qhi, hs, [&](int g) {
+          const int len = F.len[g];
+          ++n;
+          nl_sum += len < kNpyBuf ? F.nl1[g] : numpy_leaves(S, len);
+          am |= 1ull << g;
+        });
         if (ROLL && n > 0) clade = S.anc[clade];   // parent^(jump + level), :431-445
       } else if (!ordered && h < h1 && scv >= P.min_scov) {
-        for (int g = 0; g < G; ++g) {
-          int lo, len, st;
-          if (g < kLoc0) {
-            lo = F.lo[g]; len = F.len[g]; st = F.st[g];
-          } else {                                   // counted only (the contig goes staged)
-            const int a = K.lstart[l0 + g], b = K.lend[l0 + g];
-            lo = min(a, b); len = max(a, b) - lo + 1; st = K.lstrand[l0 + g];
-          }
-          if (attaches(P, qlo, qhi, hs, lo, len, st)) {
-            ++n;                                     // leaves: the LDS count below 8192 sites
-            nl_sum += (g < kLoc0 && len < kNpyBuf) ? F.nl1[g] : leaves_for(S, len);
-            if (g < kLoc0) am |= 1ull << g;
-          }
-        }
+        each_attached<false>(P, Vall, 0, G, qlo, qhi, hs, [&](int g) {
+          const int len = Vall.at(g).len();
+          ++n;                                       // leaves: the LDS count below 8192 sites
+          nl_sum += (g < kLoc0 && len < kNpyBuf) ? F.nl1[g] : numpy_leaves(S, len);
+          if (g < kLoc0) am |= 1ull << g;
+        });
         if (ROLL && n > 0) clade = S.anc[clade];   // parent^(jump + level), :431-445
       }
       int total;
@@ -844,24 +813,17 @@ __global__ __launch_bounds__(64, FULL ? 2 : (ROLL ? kRollWaves : 4)) void k_wave
       if (!staged && n > 0 && n_att + o + n <= CAP) {
         if (!ROLL)
           for (int j = 0; j < P.jump; ++j) clade = K.parent[clade];   // orgscorer.py:955-957
-        const bool ann = m != 0 && sc >= P.annot_ref;
+        const bool ann = annotates(P, m, sc);
         int slot = n_att + o;
         for (uint64_t bits = am; bits; bits &= bits - 1, ++slot) {
           const int g = __builtin_ctzll(bits);
-          const int len = F.len[g];
-          const int h1s = max(0, qlo - F.lo[g]);
-          const int h2s = min(len - 1, qhi - F.lo[g]);
-          const int start = min(h1s, len);
-          int stop = h2s + 1;                        // site[h1:h2+1], python slice rules
-          if (stop < 0) { stop += len; if (stop < 0) stop = 0; }
+          const SiteRange r = site_range(qlo, qhi, F.lo[g], F.len[g]);
           F.key[slot] = ((uint32_t)clade << kCladeShift) | ((uint32_t)g << kSlotBits) | (uint32_t)slot;
-          F.lohi[slot] = (uint32_t)start | ((uint32_t)stop << 16);
+          F.lohi[slot] = (uint32_t)r.start | ((uint32_t)r.stop << 16);
           F.sc[slot] = sc;
           F.hit()[slot] = (int)h;
           F.sm()[slot] = (int)m;
-          if (ann)                                   // annotation pass 1: best score bits (:383-392)
-            for (int b = 0; b < nsys; ++b)
-              if ((m >> b) & 1u) atomicMax(&F.abest()[g * nsys + b], dbits(sc));
+          if (ann) annot_best_score(F.abest(), g * nsys, nsys, m, sc);   // annotation pass 1
         }
       }
       n_att += total;
@@ -875,15 +837,13 @@ __global__ __launch_bounds__(64, FULL ? 2 : (ROLL ? kRollWaves : 4)) void k_wave
     WSTAT(17, n_att);
     WSTAT(23, h1 - h0);
     if (!staged && G > 0 && ann_on) {
-      // annotation pass 2: the last hit (largest index) at the best score per (locus, system)
-      for (int t = lane; t < n_att; t += 64) {
+      for (int t = lane; t < n_att; t += 64) {       // annotation pass 2
+
         const uint32_t m = (uint32_t)F.sm()[t];
         const double sc = F.sc[t];
-        if (m == 0 || !(sc >= P.annot_ref)) continue;
+        if (!annotates(P, m, sc)) continue;
         const int g = (int)((F.key[t] >> kSlotBits) & (kLoc0 - 1));
-        const int h = F.hit()[t];
-        for (int b = 0; b < nsys; ++b)
-          if (((m >> b) & 1u) && F.abest()[g * nsys + b] == dbits(sc)) atomicMax(&F.ahit()[g * nsys + b], h);
+        annot_last_hit(F.abest(), F.ahit(), g * nsys, nsys, m, sc, F.hit()[t]);
       }
       wave_sync();
       if (lane < nann) K.annot[l0 * nsys + lane] = F.ahit()[lane];

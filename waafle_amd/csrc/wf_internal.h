@@ -17,6 +17,13 @@ constexpr int kNpyBuf = 8192;           // numpy reduction buffer (NPY_BUFSIZE)
 // systems 0-5 << 26 (k_pack_keys packs it when the caller passes none)
 constexpr uint32_t kKeyTaxon = (1u << 24) - 1u, kKeyScov = 1u << 24, kKeyMinus = 1u << 25;
 constexpr int kKeySys = 26;
+__host__ __device__ inline uint32_t pack_hit_key(int32_t taxon, bool scov_ok, bool minus, uint32_t sysmask) {
+  return (uint32_t)taxon | (scov_ok ? kKeyScov : 0u) | (minus ? kKeyMinus : 0u) | (sysmask & 63u) << kKeySys;
+}
+__host__ __device__ inline bool key_scov(uint32_t k) { return (k & kKeyScov) != 0u; }
+__host__ __device__ inline int key_minus(uint32_t k) { return (k & kKeyMinus) ? 1 : 0; }   // the strand code of '-'
+__host__ __device__ inline int key_taxon(uint32_t k) { return (int)(k & kKeyTaxon); }
+__host__ __device__ inline uint32_t key_systems(uint32_t k) { return k >> kKeySys; }
 constexpr int kLeafSlots = 160;         // >= leaves of one 8192-element buffer
 constexpr int kMaxIter = 100;           // orgscorer.py:580
 constexpr int kLin = 16;                // lineage row: ancestors at depths 0..15 (64 B)

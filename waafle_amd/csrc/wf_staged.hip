@@ -31,7 +31,7 @@
 #include <string>
 #include <vector>
 
-#include "wf_device.h"
+#include "wf_attach.h"
 
 namespace wf {
 
@@ -106,10 +106,6 @@ constexpr int kAttNTBig = 512;   // ... or 8 when the batch's contigs have thous
 constexpr int kAttBigHits = 2048;   // cfg5 stress shape: one wave stepped ~80 dependent chunks)
 constexpr int kAttLoc = 128;      // loci staged in LDS (more: read from HBM)
 
-struct LocView {
-  int lo, len, st;
-};
-
 template <int PASS, int NT>
 // (S_arg first: the per-contig loop re-reads the argument block through kernarg_fresh)
 __global__ __launch_bounds__(NT) void k_att_contig(const SArgs S_arg, int64_t* ccnt,
@@ -133,14 +129,11 @@ __global__ __launch_bounds__(NT) void k_att_contig(const SArgs S_arg, int64_t* c
     const bool lds_loc = G <= kAttLoc;
     if (lds_loc)
       for (int g = tid; g < G; g += NT) {
-        const int a = K.lstart[l0 + g], b = K.lend[l0 + g];
-        s_lo[g] = min(a, b);
-        const int len = max(a, b) - min(a, b) + 1;
-        s_len[g] = len;
-        s_st[g] = K.lstrand[l0 + g];
-        if (PASS == 0)
-          s_nl[g] = (len / kNpyBuf) * (S.lut_off[kNpyBuf + 1] - S.lut_off[kNpyBuf]) +
-                    (S.lut_off[len % kNpyBuf + 1] - S.lut_off[len % kNpyBuf]);
+        const Locus L = load_locus(K, l0 + g);
+        s_lo[g] = L.lo;
+        s_len[g] = L.len();
+        s_st[g] = L.st;
+        if (PASS == 0) s_nl[g] = numpy_leaves(S, L.len());
       }
     const int ns = K.n_sys;
     const bool hkey = K.hkey != nullptr && ns <= 6;  // (the key holds systems 0-5)
@@ -148,36 +141,26 @@ __global__ __launch_bounds__(NT) void k_att_contig(const SArgs S_arg, int64_t* c
     if (lds_ann)
       for (int i = tid; i < G * ns; i += NT) { s_best[i] = 0ull; s_hit[i] = -1; }
     __syncthreads();
-    auto locus = [&](int g) -> LocView {
-      if (lds_loc) return LocView{s_lo[g], s_len[g], s_st[g]};
-      const int a = K.lstart[l0 + g], b = K.lend[l0 + g];
-      return LocView{min(a, b), max(a, b) - min(a, b) + 1, K.lstrand[l0 + g]};
-    };
-    // loci ascending and disjoint (the usual GFF) with min_overlap > 0: a hit attaches only to
-    // loci it overlaps, a run found by binary search (the wave kernels' rule) instead of a
-    // test against every locus -- O(H log G) rather than O(H G) for the cfg5 stress contigs
-    bool ordered = lds_loc && P.min_overlap > 0.0;
+    const LociByLen V{s_lo, s_len, s_st};
+    const LociOrBatch Vall{V, K, l0, lds_loc ? G : 0};   // (more than kAttLoc loci: none staged)
+    // the ordered-loci search of the wave kernels (wf_attach.h), block-wide: it is what keeps
+    // the cfg5 stress contigs at O(H log G)
+    bool ordered = lds_loc && P.min_overlap > 0.0 && G > 0;   // (G > 0: the search reads a locus)
     if (ordered) {
       bool bad = false;
-      for (int g = 1 + tid; g < G; g += NT) bad = bad || s_lo[g] <= s_lo[g - 1] + s_len[g - 1] - 1;
+      for (int g = 1 + tid; g < G; g += NT) bad = bad || locus_out_of_order(V.lo(g), V.hi(g - 1));
       ordered = !__syncthreads_or(bad);
     }
-    // the loci hit h attaches to, in GFF order: f(g, L) for each
+    // the loci hit h attaches to, in GFF order: f(g, lo, len) for each
     auto each_locus = [&](int qlo, int qhi, int hs, auto f) {
       if (ordered) {
-        int g = 0;                                   // first locus ending at or after qlo
-        for (int k = 64; k > 0; k >>= 1)
-          if (g + k <= G && s_lo[g + k - 1] + s_len[g + k - 1] - 1 < qlo) g += k;
-        for (; g < G; ++g) {
-          const LocView L{s_lo[g], s_len[g], s_st[g]};
-          if (L.lo > qhi) break;
-          if (attaches(P, qlo, qhi, hs, L.lo, L.len, L.st)) f(g, L);
-        }
-        return;
-      }
-      for (int g = 0; g < G; ++g) {
-        const LocView L = locus(g);
-        if (attaches(P, qlo, qhi, hs, L.lo, L.len, L.st)) f(g, L);
+        const int g0 = first_locus<kAttLoc>(G, qlo, [&](int g) { return V.hi(g); });
+        each_attached<true>(P, V, g0, G, qlo, qhi, hs, [&](int g) { f(g, s_lo[g], s_len[g]); });
+      } else {
+        each_attached<false>(P, Vall, 0, G, qlo, qhi, hs, [&](int g) {
+          const Locus L = Vall.at(g);
+          f(g, L.lo, L.len());
+        });
       }
     };
     long long n_tot = 0, nl_tot = 0;
@@ -195,13 +178,13 @@ __global__ __launch_bounds__(NT) void k_att_contig(const SArgs S_arg, int64_t* c
         if (PASS == 1) sc = K.score[h];
         if (hkey) {                                 // the packed word: 20 B a hit instead of 33
           const uint32_t k = K.hkey[h];
-          scov_ok = (k & kKeyScov) != 0u;
-          hs = P.stranded && (k & kKeyMinus) ? 1 : 0;
-          clade = (int)(k & kKeyTaxon);
-          m = k >> kKeySys;
+          scov_ok = key_scov(k);
+          hs = key_minus(k);
+          clade = key_taxon(k);
+          m = key_systems(k);
         } else {
           scov_ok = K.scov[h] >= P.min_scov;
-          hs = P.stranded ? K.hstrand[h] : 0;
+          hs = P.stranded ? K.hstrand[h] : 0;  // (the strand only matters --stranded)
           if (PASS == 1) {
             clade = K.taxon[h];
             m = ns > 0 ? K.sysmask[h] : 0u;
@@ -210,12 +193,9 @@ __global__ __launch_bounds__(NT) void k_att_contig(const SArgs S_arg, int64_t* c
       }
       const bool live = h < h1 && scov_ok;
       if (live) {
-        each_locus(qlo, qhi, hs, [&](int g, const LocView& L) {
+        each_locus(qlo, qhi, hs, [&](int g, int, int len) {
           ++n;
-          if (PASS == 0)
-            nl += lds_loc ? s_nl[g]
-                          : (L.len / kNpyBuf) * (S.lut_off[kNpyBuf + 1] - S.lut_off[kNpyBuf]) +
-                                (S.lut_off[L.len % kNpyBuf + 1] - S.lut_off[L.len % kNpyBuf]);
+          if (PASS == 0) nl += lds_loc ? s_nl[g] : numpy_leaves(S, len);
         });
       }
       if (PASS == 0) {
@@ -243,26 +223,19 @@ __global__ __launch_bounds__(NT) void k_att_contig(const SArgs S_arg, int64_t* c
       base += total;
       if (n == 0) continue;
       for (int j = 0; j < P.jump; ++j) clade = K.parent[clade];   // orgscorer.py:955-957
-      const bool ann = m != 0 && sc >= P.annot_ref;
-      each_locus(qlo, qhi, hs, [&](int g, const LocView& L) {
-        const int h1s = max(0, qlo - L.lo);
-        const int h2s = min(L.len - 1, qhi - L.lo);
-        const int start = min(h1s, L.len);
-        int stop = h2s + 1;                        // site[h1:h2+1], python slice rules
-        if (stop < 0) { stop += L.len; if (stop < 0) stop = 0; }
-        S.att_lo[o] = start;
-        S.att_hi[o] = stop;                        // empty when stop <= start
+      const bool ann = annotates(P, m, sc);
+      each_locus(qlo, qhi, hs, [&](int g, int lo, int len) {
+        const SiteRange r = site_range(qlo, qhi, lo, len);
+        S.att_lo[o] = r.start;
+        S.att_hi[o] = r.stop;                      // empty when stop <= start
         S.att_loc[o] = g;
         S.att_clade[o] = clade;
         S.att_hit[o] = (int)h;
         S.att_sc[o] = sc;
         ++o;
-        if (ann) {                                  // annotation pass 1: best score bits
-          for (int b = 0; b < ns; ++b) {
-            if (!((m >> b) & 1u)) continue;
-            if (lds_ann) atomicMax(&s_best[g * ns + b], dbits(sc));
-            else atomicMax(reinterpret_cast<unsigned long long*>(&S.annot_best[(l0 + g) * ns + b]), dbits(sc));
-          }
+        if (ann) {                                  // annotation pass 1
+          if (lds_ann) annot_best_score(s_best, g * ns, ns, m, sc);
+          else annot_best_score(S.annot_best + l0 * ns, g * ns, ns, m, sc);
         }
       });
     }
@@ -285,24 +258,17 @@ __global__ __launch_bounds__(NT) void k_att_contig(const SArgs S_arg, int64_t* c
       continue;
     }
     if (ns > 0) {
-      // annotation pass 2: the last hit (largest index) at the best score, per (locus,
-      // system); every attachment of this contig is in [catt_off[c], base)
+      // annotation pass 2: every attachment of this contig is in [catt_off[c], base)
       __syncthreads();
       const int64_t a0 = S.catt_off[c];
       for (int64_t a = a0 + tid; a < base; a += NT) {
         const int h = S.att_hit[a];
-        const uint32_t m = hkey ? K.hkey[h] >> kKeySys : K.sysmask[h];
+        const uint32_t m = hkey ? key_systems(K.hkey[h]) : K.sysmask[h];
         const double sc = S.att_sc[a];
-        if (m == 0 || !(sc >= P.annot_ref)) continue;
+        if (!annotates(P, m, sc)) continue;
         const int g = S.att_loc[a];
-        for (int b = 0; b < ns; ++b) {
-          if (!((m >> b) & 1u)) continue;
-          if (lds_ann) {
-            if (s_best[g * ns + b] == dbits(sc)) atomicMax(&s_hit[g * ns + b], h);
-          } else if (S.annot_best[(l0 + g) * ns + b] == dbits(sc)) {
-            atomicMax(&K.annot[(l0 + g) * ns + b], h);
-          }
-        }
+        if (lds_ann) annot_last_hit(s_best, s_hit, g * ns, ns, m, sc, h);
+        else annot_last_hit(S.annot_best + l0 * ns, K.annot + l0 * ns, g * ns, ns, m, sc, h);
       }
       __syncthreads();
       if (lds_ann)

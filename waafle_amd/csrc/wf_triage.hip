@@ -2,8 +2,8 @@
 // settles from the clades present on every locus, decided without a sort.
 //
 // One wave64 per contig, alone in its workgroup (no barriers), persistent over the batch in
-// the XCD-aware order of the wave kernels (wf_fast.hip).  Per contig (orgscorer.py:359-429,
-// 447-461, 585-597, 621-631):
+// the XCD-aware order of the wave kernels (xcd_order, wf_attach.h).  Per contig
+// (orgscorer.py:359-429, 447-461, 585-597, 621-631):
 //   hits -> attachments     lane per hit, up to 4 batches of 64 held in registers; the loci
 //                           (ascending, disjoint) in LDS, each hit's first candidate locus by
 //                           binary search (orgscorer.py:359-369, calc_overlap utils.py:487-500)
@@ -27,7 +27,7 @@
 // from their hits, as it runs every contig without the triage.  Same arithmetic, so the same
 // bits: the triage only skips the sort, the segment table and the pruning passes the wave
 // form spends on the contigs explain_one settles at level 0 (~90% at cfg4).
-#include "wf_device.h"
+#include "wf_attach.h"
 #include "wf_lanes.h"
 
 
@@ -42,7 +42,6 @@ constexpr int kTrTab = 128;            // candidate table: clades attached to lo
 constexpr int kTrSeg = 64;             // full clades x loci evaluated (one lane each)
 constexpr int kTrSpan = 26;            // loci one hit may attach to, from its first candidate
 constexpr uint32_t kTrEmpty = 0xFFFFFFFFu;
-constexpr int kTrXcds = 8;             // MI355X: 8 XCDs of 32 CUs, each with its own L2
 constexpr int kTrWaves = 8;            // resident waves per SIMD (64 VGPRs, ~12 spilled; a 4.8 KB slice).
                                        // Same box (r5c): 3.66 ms per cfg4 pass against 3.85 at 6
                                        // waves per SIMD (75 VGPRs, none spilled)
@@ -70,25 +69,13 @@ static_assert(sizeof(TriSmem) <= 160 * 1024 / (4 * kTrWaves), "triage slice: kTr
 
 __device__ __forceinline__ uint32_t tr_hash(uint32_t clade) { return (clade * 0x9E3779B1u) >> 25; }   // 7 bits
 
-// Site range [start, stop) of a hit on a locus (orgscorer.py:371-382, python slice rules),
-// packed lo | hi << 16 (loci < 8192 sites here).
-__device__ __forceinline__ uint32_t tr_lohi(int qlo, int qhi, int llo, int len) {
-  const int h1s = max(0, qlo - llo);
-  const int h2s = min(len - 1, qhi - llo);
-  const int start = min(h1s, len);
-  int stop = h2s + 1;
-  if (stop < 0) { stop += len; if (stop < 0) stop = 0; }
-  return (uint32_t)start | ((uint32_t)stop << 16);
-}
-
 // The packed hit word (wf_batch.hit_key, kKey* in wf_internal.h).  After the table pass the
 // low 24 bits hold the clade's table slot + 1.
 
 // wf_batch.hit_key when the caller passes none (include/waafle_hip.h)
 __global__ void k_pack_keys(const KArgs K, int64_t n_hits, uint32_t* key) {
   for (int64_t h = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; h < n_hits; h += (int64_t)gridDim.x * blockDim.x)
-    key[h] = (uint32_t)K.taxon[h] | (K.scov[h] >= K.p.min_scov ? kKeyScov : 0u) | (K.hstrand[h] == 1 ? kKeyMinus : 0u) |
-             (K.n_sys > 0 ? (K.sysmask[h] & 63u) << kKeySys : 0u);
+    key[h] = pack_hit_key(K.taxon[h], K.scov[h] >= K.p.min_scov, K.hstrand[h] == 1, K.sysmask[h]);
 }
 
 // SYSKEY: the annotation systems come from the key (n_systems <= 6); else from hit_sysmask.
@@ -98,11 +85,9 @@ __global__ __launch_bounds__(64, kTrWaves) void k_triage(const SArgs S_arg, int6
   __shared__ TriSmem F;
   const int lane = threadIdx.x;
   const int N = S_arg.k.n_contigs;
-  // XCD-aware order (k_wave): XCD x's j-th workgroup takes contig (8 k + x) * B + j at step k
-  const bool xmap = gridDim.x % kTrXcds == 0;
-  const int xb = (int)gridDim.x / kTrXcds, xj = (int)blockIdx.x / kTrXcds, xx = (int)blockIdx.x % kTrXcds;
+  const XcdOrder order = xcd_order();
   for (int it = 0;; ++it) {
-    const int c = xmap ? (it * kTrXcds + xx) * xb + xj : (int)blockIdx.x + it * (int)gridDim.x;
+    const int c = order.at(it);
     if (c >= N) break;
     TLAP_MARK();
     const SArgs& S = kernarg_fresh<SArgs>(S_arg);
@@ -135,24 +120,19 @@ __global__ __launch_bounds__(64, kTrWaves) void k_triage(const SArgs S_arg, int6
         if (!SYSKEY && nsys > 0) r_m[b] = K.sysmask[h];
       }
     }
-    auto sysm = [&](int b) -> uint32_t { return SYSKEY ? r_k[b] >> kKeySys : r_m[b]; };
+    auto sysm = [&](int b) -> uint32_t { return SYSKEY ? key_systems(r_k[b]) : r_m[b]; };
     const int64_t l0 = K.loc_off[c];
     const int G = (int)(K.loc_off[c + 1] - l0);
-    int my_lo = 0, my_hi = -1, my_st = 0;
-    if (lane < G && G <= kTrLoc) {
-      const int a = K.lstart[l0 + lane], e = K.lend[l0 + lane];
-      my_lo = min(a, e);
-      my_hi = max(a, e);
-      my_st = K.lstrand[l0 + lane];
-    }
-    const int prev_hi = __shfl_up(my_hi, 1, 64);
+    Locus my{0, -1, 0};
+    if (lane < G && G <= kTrLoc) my = load_locus(K, l0 + lane);
+    const int prev_hi = __shfl_up(my.hi, 1, 64);
     // what the triage takes (else the wave form): loci ascending and disjoint (each hit's
     // loci found by binary search), every locus one numpy buffer, options only on full
     // clades (k1 > 0), the weak-locus mask from the full clades' means
     const bool take =
         nh > 0 && nh <= 64 * kTrHB && G > 0 && G <= kTrLoc && G * nsys <= kTrLoc && P.min_overlap > 0.0 &&
         P.k1 > 0.0 && P.weak != 2 &&
-        __ballot(lane < G && ((lane >= 1 && my_lo <= prev_hi) || my_hi - my_lo + 1 >= kNpyBuf)) == 0ull;
+        __ballot(lane < G && ((lane >= 1 && locus_out_of_order(my.lo, prev_hi)) || my.len() >= kNpyBuf)) == 0ull;
     if (!take) {
       hand_on();
       continue;
@@ -160,7 +140,7 @@ __global__ __launch_bounds__(64, kTrWaves) void k_triage(const SArgs S_arg, int6
     const uint64_t allG = G >= 64 ? ~0ull : ((1ull << G) - 1ull);
     const int nann = G * nsys;
     const bool ann_on = nsys > 0;
-    if (lane < G) { F.lo[lane] = my_lo; F.hi[lane] = my_hi; F.st[lane] = (int8_t)my_st; }
+    if (lane < G) { F.lo[lane] = my.lo; F.hi[lane] = my.hi; F.st[lane] = (int8_t)my.st; }
     F.tkey[lane] = kTrEmpty; F.tkey[lane + 64] = kTrEmpty;
     F.tmask[lane] = 0ull; F.tmask[lane + 64] = 0ull;
     F.abest[lane] = 0ull; F.ahit[lane] = -1;
@@ -175,27 +155,24 @@ __global__ __launch_bounds__(64, kTrWaves) void k_triage(const SArgs S_arg, int6
 #pragma unroll
     for (int b = 0; b < kTrHB; ++b) {
       uint32_t am = 0u;
-      if (h0 + 64 * b + lane < hend && (r_k[b] & kKeyScov)) {
+      if (h0 + 64 * b + lane < hend && key_scov(r_k[b])) {
         const int qlo = r_qlo[b], qhi = r_qhi[b];
-        int g = 0;
-#pragma unroll
-        for (int k = 32; k > 0; k >>= 1) {
-          const int gk = g + k;                      // (a select, not a branch per step)
-          g = (gk <= G && F.hi[min(gk, G) - 1] < qlo) ? gk : g;
-        }
+        int g = first_locus<kTrLoc>(G, qlo, [&](int i) { return F.hi[i]; });
         const int g0 = g;
         uint32_t rel = 0u;
+        // (each_attached's walk, kept as a loop of its own: behind the shared helper the
+        // register allocation of a kernel this close to its 64 VGPRs moves)
         for (; g < G; ++g) {
           const int lo = F.lo[g];
           if (lo > qhi) break;
-          if (attaches(P, qlo, qhi, (r_k[b] & kKeyMinus) ? 1 : 0, lo, F.hi[g] - lo + 1, F.st[g])) {
+          if (attaches(P, qlo, qhi, key_minus(r_k[b]), lo, F.hi[g] - lo + 1, F.st[g])) {
             if (g - g0 < kTrSpan) rel |= 1u << (g - g0);
             else bad = true;
           }
         }
         if (rel) {
           am = (uint32_t)g0 | (rel << 6);
-          int cl = (int)(r_k[b] & kKeyTaxon);
+          int cl = key_taxon(r_k[b]);
           for (int j = 0; j < P.jump; ++j) cl = K.parent[cl];           // orgscorer.py:955-957
           r_k[b] = (r_k[b] & ~kKeyTaxon) | (uint32_t)cl;
         }
@@ -242,12 +219,9 @@ __global__ __launch_bounds__(64, kTrWaves) void k_triage(const SArgs S_arg, int6
           slot = (slot + 1) & (kTrTab - 1);
         }
         const uint32_t m = sysm(b);
-        if (ann_on && m != 0u && r_sc[b] >= P.annot_ref)
-          for (uint64_t bits = lm; bits; bits &= bits - 1) {
-            const int g = __builtin_ctzll(bits);
-            for (int s = 0; s < nsys; ++s)
-              if ((m >> s) & 1u) atomicMax(&F.abest[g * nsys + s], dbits(r_sc[b]));
-          }
+        if (ann_on && annotates(P, m, r_sc[b]))
+          for (uint64_t bits = lm; bits; bits &= bits - 1)
+            annot_best_score(F.abest, __builtin_ctzll(bits) * nsys, nsys, m, r_sc[b]);
       }
       r_k[b] = (r_k[b] & ~kKeyTaxon) | (uint32_t)(found + 1);
     }
@@ -287,7 +261,8 @@ __global__ __launch_bounds__(64, kTrWaves) void k_triage(const SArgs S_arg, int6
             const int g = g0 + __builtin_ctz(rel);
             const int q = fi * G + g;
             const int llo = F.lo[g], len = F.hi[g] - llo + 1;
-            const uint32_t lh = tr_lohi(r_qlo[b], r_qhi[b], llo, len);
+            const SiteRange r = site_range(r_qlo[b], r_qhi[b], llo, len);
+            const uint32_t lh = (uint32_t)r.start | ((uint32_t)r.stop << 16);   // (loci < 8192 sites here)
             atomicAdd(&F.scnt[q], 1);
             F.slohi[q] = lh;
             // (k_wave's Fw: the best whole-locus score above 0.0; an attachment k_wave keeps
@@ -301,8 +276,7 @@ __global__ __launch_bounds__(64, kTrWaves) void k_triage(const SArgs S_arg, int6
           const int h = (int)(h0 + 64 * b + lane);
           for (uint64_t bits = (uint64_t)(am >> 6) << g0; bits; bits &= bits - 1) {
             const int g = __builtin_ctzll(bits);
-            for (int s = 0; s < nsys; ++s)
-              if (((m >> s) & 1u) && F.abest[g * nsys + s] == dbits(r_sc[b])) atomicMax(&F.ahit[g * nsys + s], h);
+            annot_last_hit(F.abest, F.ahit, g * nsys, nsys, m, r_sc[b], h);
           }
         }
       }
@@ -439,30 +413,23 @@ __global__ __launch_bounds__(64, kTrWaves) void k_triage(const SArgs S_arg, int6
 __global__ __launch_bounds__(64) void k_count(const SArgs S, int64_t* ccnt, int64_t* cleaves, int32_t* pend) {
   __shared__ int s_lo[kTrLoc], s_hi[kTrLoc], s_nl[kTrLoc];
   __shared__ int8_t s_st[kTrLoc];
+  const LociByEnd V{s_lo, s_hi, s_st};
   const KArgs& K = S.k;
   const DevParams& P = K.p;
   const int lane = threadIdx.x;
   unsigned long long n_staged = 0;
-  auto leaves = [&](int len) {                       // numpy leaves of a locus (the LUT's counts)
-    return (len / kNpyBuf) * (S.lut_off[kNpyBuf + 1] - S.lut_off[kNpyBuf]) +
-           (S.lut_off[len % kNpyBuf + 1] - S.lut_off[len % kNpyBuf]);
-  };
   for (int c = blockIdx.x; c < K.n_contigs; c += gridDim.x) {
     const int64_t h0 = K.hit_off[c], h1 = K.hit_off[c + 1];
     if (h1 - h0 <= kTrBig) continue;                 // (k_triage handed it on: pend kPendTriage)
     const int64_t l0 = K.loc_off[c];
     const int G = (int)(K.loc_off[c + 1] - l0);
-    int clo = 0, chi = -1, cst = 0;
-    if (lane < G && G <= kTrLoc) {
-      const int a = K.lstart[l0 + lane], e = K.lend[l0 + lane];
-      clo = min(a, e);
-      chi = max(a, e);
-      cst = K.lstrand[l0 + lane];
+    Locus my{0, -1, 0};
+    if (lane < G && G <= kTrLoc) my = load_locus(K, l0 + lane);
+    if (!(G > 0 && G <= kTrLoc && P.min_overlap > 0.0 && wave_loci_ordered(lane, G, my.lo, my.hi))) continue;
+    if (lane < G) {
+      s_lo[lane] = my.lo; s_hi[lane] = my.hi; s_st[lane] = (int8_t)my.st;
+      s_nl[lane] = numpy_leaves(S, my.len());
     }
-    const int cprev = __shfl_up(chi, 1, 64);
-    if (!(G > 0 && G <= kTrLoc && P.min_overlap > 0.0 && __ballot(lane < G && lane >= 1 && clo <= cprev) == 0ull))
-      continue;
-    if (lane < G) { s_lo[lane] = clo; s_hi[lane] = chi; s_st[lane] = (int8_t)cst; s_nl[lane] = leaves(chi - clo + 1); }
     wave_sync();
     long long n_att = 0, nl = 0;
     for (int64_t hb = h0; hb < h1; hb += 64 * kCntR) {   // kCntR batches' loads issued together
@@ -476,21 +443,13 @@ __global__ __launch_bounds__(64) void k_count(const SArgs S, int64_t* ccnt, int6
       }
 #pragma unroll
       for (int r = 0; r < kCntR; ++r) {
-        if (hb + 64 * r + lane >= h1 || !(r_k[r] & kKeyScov)) continue;
-        const int qlo = r_qlo[r], qhi = r_qhi[r], hs = (r_k[r] & kKeyMinus) ? 1 : 0;
-        int g = 0;
-#pragma unroll
-        for (int k = 32; k > 0; k >>= 1)
-          if (g + k <= G && s_hi[g + k - 1] < qlo) g += k;
-        for (; g < G; ++g) {
-          const int lo = s_lo[g];
-          if (lo > qhi) break;
-          const int len = s_hi[g] - lo + 1;
-          if (attaches(P, qlo, qhi, hs, lo, len, s_st[g])) {
-            ++n_att;
-            nl += s_nl[g];                             // (per locus, staged above: no table loads here)
-          }
-        }
+        if (hb + 64 * r + lane >= h1 || !key_scov(r_k[r])) continue;
+        const int qlo = r_qlo[r], qhi = r_qhi[r];
+        const int g0 = first_locus<kTrLoc>(G, qlo, [&](int g) { return V.hi(g); });
+        each_attached<true>(P, V, g0, G, qlo, qhi, key_minus(r_k[r]), [&](int g) {
+          ++n_att;
+          nl += s_nl[g];                               // (per locus, staged above: no table loads here)
+        });
       }
     }
     n_att = wave_sum_dpp(n_att);
