@@ -28,7 +28,8 @@ extern "C" {
                                  5: WF_OPT_TRIAGE, WF_PHASE_TRIAGE;
                                  6: wf_batch.hit_key (packed hit record), wf_pack_hit_keys;
                                     WF_OPT_WAVE_TWO 0 (the round-3 hand-over flow) retired;
-                                    still 6 (additive): wf_map_index, wf_map_pairs */
+                                    still 6 (additive): wf_map_index, wf_map_pairs;
+                                    still 6 (additive): wf_map_pairs_gapped */
 
 enum wf_status {
   WF_OK = 0,
@@ -311,7 +312,8 @@ int wf_junctions(wf_ctx* ctx, const wf_jn_batch* batch, const wf_jn_params* para
  * alignments inside one contig with at most max_mm mismatches, and of the concordant pairs
  * (same contig, opposite strands, no dovetail, min_insert <= fragment <= max_insert) the
  * one with the least (mm1 + mm2, contig, + mate's position, fragment, mate-1 strand).
- * No gaps, no clipping, no MAPQ: reads with indels stay unaligned. */
+ * No gaps, no clipping, no MAPQ: reads with indels stay unaligned (but see
+ * wf_map_pairs_gapped below). */
 typedef struct wf_map_params {
   int32_t seed_len;           /* S, 12..32 (default 20) */
   int32_t max_occ;            /* 1..64 (default 16) */
@@ -355,6 +357,32 @@ int wf_map_index(wf_ctx* ctx, const wf_map_contigs* contigs, const wf_map_params
 /* params: seed_len and max_occ must equal the index's (WF_E_BADINPUT); WF_E_STATE before
    wf_map_index */
 int wf_map_pairs(wf_ctx* ctx, const wf_map_reads* reads, const wf_map_params* params, wf_map_result* out);
+
+/* Single-gap rescue ("gapped pass").  wf_map_pairs_gapped is wf_map_pairs
+ * followed, for max_gap > 0, by a second pass over the pairs it left unaligned whose mates
+ * are both at least seed_len long: each mate may then carry one deletion (d > 0: d contig
+ * bases the read lacks) or one insertion (d < 0: -d read bases) of at most max_gap bases
+ * after its first k bases (k counted along the contig's + strand), both segments at least
+ * seed_len long.  Pairs that wf_map_pairs aligns keep exactly its result.  mm1 / mm2 stay
+ * mismatch counts; a mate spans L + d contig bases. */
+typedef struct wf_map_gap_params {
+  int32_t max_gap;            /* 0..8 (default 0: no gapped pass) */
+  int32_t _pad[3];
+} wf_map_gap_params;
+
+typedef struct wf_map_gap_result { /* [n_pairs] each, same residency as the reads */
+  int8_t* d1;                 /* gap of mate 1: > 0 deletion, < 0 insertion, 0 none */
+  int8_t* d2;
+  int16_t* k1;                /* bases of mate 1's variant before its gap (0 when d1 = 0) */
+  int16_t* k2;
+  uint8_t* flags;             /* bit 0: aligned by the gapped pass; bit 1: a mate had more
+                                 than 256 hits in the gapped pass (the pair stays unaligned) */
+} wf_map_gap_result;
+
+/* As wf_map_pairs, plus gap_params->max_gap outside 0..8: WF_E_BADINPUT.  With max_gap 0 it
+   writes what wf_map_pairs writes and zeros in gap_out.  Returns after the work is done. */
+int wf_map_pairs_gapped(wf_ctx* ctx, const wf_map_reads* reads, const wf_map_params* params,
+                        const wf_map_gap_params* gap_params, wf_map_result* out, wf_map_gap_result* gap_out);
 
 /* ---- --write-details (orgscorer.py:766-812, 931-937) --------------------------------
  * With details on, the next wf_score (staged mode) also records, for every roll-up level,

@@ -712,14 +712,15 @@ int wf_map_index(wf_ctx* ctx, const wf_map_contigs* c, const wf_map_params* p) {
   return rc ? fail(ctx, rc, "%s", err.c_str()) : WF_OK;
 }
 
-int wf_map_pairs(wf_ctx* ctx, const wf_map_reads* rd, const wf_map_params* p, wf_map_result* r) {
-  if (!ctx) return WF_E_BADINPUT;
-  if (!rd || !p || !r) return fail(ctx, WF_E_BADINPUT, "null reads/params/result");
+// the checks wf_map_pairs and wf_map_pairs_gapped share; *run: there are pairs to map
+static int check_map_call(wf_ctx* ctx, const wf_map_reads* rd, const wf_map_params* p, const wf_map_result* r,
+                          const char* who, bool* run) {
+  *run = false;
   if (rd->n_pairs < 0 || rd->n_pairs >= ((int64_t)1 << 31)) return fail(ctx, WF_E_BADINPUT, "n_pairs outside [0, 2^31)");
   int rc = check_map_params(ctx, p, true);
   if (rc) return rc;
   int S = 0, occ = 0;
-  if (!wf::map_index_params(ctx->map, &S, &occ)) return fail(ctx, WF_E_STATE, "wf_map_pairs before wf_map_index");
+  if (!wf::map_index_params(ctx->map, &S, &occ)) return fail(ctx, WF_E_STATE, "%s before wf_map_index", who);
   if (S != p->seed_len || occ != p->max_occ)
     return fail(ctx, WF_E_BADINPUT, "seed_len %d / max_occ %d differ from the index's %d / %d", p->seed_len,
                 p->max_occ, S, occ);
@@ -727,12 +728,41 @@ int wf_map_pairs(wf_ctx* ctx, const wf_map_reads* rd, const wf_map_params* p, wf
   if (!rd->off1 || !rd->off2 || !rd->seq1 || !rd->seq2) return fail(ctx, WF_E_BADINPUT, "null read arrays");
   if (!r->contig || !r->pos1 || !r->pos2 || !r->strand1 || !r->mm1 || !r->mm2)
     return fail(ctx, WF_E_BADINPUT, "null result arrays");
+  *run = true;
+  return WF_OK;
+}
+
+int wf_map_pairs(wf_ctx* ctx, const wf_map_reads* rd, const wf_map_params* p, wf_map_result* r) {
+  if (!ctx) return WF_E_BADINPUT;
+  if (!rd || !p || !r) return fail(ctx, WF_E_BADINPUT, "null reads/params/result");
+  bool run = false;
+  int rc = check_map_call(ctx, rd, p, r, "wf_map_pairs", &run);
+  if (rc || !run) return rc;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const wf::MapReads reads{rd->n_pairs, rd->device_resident, rd->seq1, rd->off1, rd->seq2, rd->off2};
   const wf::MapRule rule{p->max_occ, p->max_mm, p->min_insert, p->max_insert};
   const wf::MapOut out{r->contig, r->pos1, r->pos2, r->strand1, r->mm1, r->mm2};
   std::string err;
   rc = wf::map_pairs(ctx->map, reads, rule, out, ctx->stream, &err);
+  return rc ? fail(ctx, rc, "%s", err.c_str()) : WF_OK;
+}
+
+int wf_map_pairs_gapped(wf_ctx* ctx, const wf_map_reads* rd, const wf_map_params* p, const wf_map_gap_params* gp,
+                        wf_map_result* r, wf_map_gap_result* gr) {
+  if (!ctx) return WF_E_BADINPUT;
+  if (!rd || !p || !gp || !r || !gr) return fail(ctx, WF_E_BADINPUT, "null reads/params/gap params/result");
+  if (gp->max_gap < 0 || gp->max_gap > 8) return fail(ctx, WF_E_BADINPUT, "max_gap %d outside 0..8", gp->max_gap);
+  bool run = false;
+  int rc = check_map_call(ctx, rd, p, r, "wf_map_pairs_gapped", &run);
+  if (rc || !run) return rc;
+  if (!gr->d1 || !gr->d2 || !gr->k1 || !gr->k2 || !gr->flags) return fail(ctx, WF_E_BADINPUT, "null gap result arrays");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const wf::MapReads reads{rd->n_pairs, rd->device_resident, rd->seq1, rd->off1, rd->seq2, rd->off2};
+  const wf::MapRule rule{p->max_occ, p->max_mm, p->min_insert, p->max_insert};
+  const wf::MapOut out{r->contig, r->pos1, r->pos2, r->strand1, r->mm1, r->mm2};
+  const wf::MapGapOut gout{gr->d1, gr->d2, gr->k1, gr->k2, gr->flags};
+  std::string err;
+  rc = wf::map_pairs_gapped(ctx->map, reads, rule, gp->max_gap, out, gout, ctx->stream, &err);
   return rc ? fail(ctx, rc, "%s", err.c_str()) : WF_OK;
 }
 

@@ -189,6 +189,11 @@ int map_index(MapState* st, const char* seq, const int64_t* off, int n_contigs, 
               hipStream_t s, std::string* err);                          // host arrays
 int map_pairs(MapState* st, const MapReads& rd, const MapRule& rule, const MapOut& out, hipStream_t s,
               std::string* err);
+// ... followed by the single-gap rescue of the pairs left unaligned (max_gap 0: none); the
+// gap fields are zeroed first.  Returns after the device is done.
+struct MapGapOut { int8_t* d1; int8_t* d2; int16_t* k1; int16_t* k2; uint8_t* flags; };
+int map_pairs_gapped(MapState* st, const MapReads& rd, const MapRule& rule, int max_gap, const MapOut& out,
+                     const MapGapOut& gout, hipStream_t s, std::string* err);
 
 // --write-details: per roll-up level, the evaluated (active) contigs and the segment
 // records of the level, copied to the host (wf_staged.hip details_level)

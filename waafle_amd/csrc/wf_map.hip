@@ -24,6 +24,16 @@
 //     mismatches = popcount((x ^ r) low | (x ^ r) high | N), summed per candidate in LDS
 //   (mate-1 hit, mate-2 hit) tasks over the lanes: the concordant pair of least key, by a
 //     wave-wide minimum of the two key words
+// Single-gap rescue (map_pairs_gapped, max_gap > 0; DESIGN.md §11.1 "gapped pass"):
+//   k_map_gap_flag / scan / k_map_gap_list  the pairs k_map_pairs left unaligned whose mates
+//     are both at least S long, compacted on the device
+//   k_map_gap     one wave per listed pair, in launches of at most kMapGapLaunch pairs: the
+//     same planes and seed look-ups; the candidates are now diagonals (start, contig of the
+//     seed occurrence, the set of seed slots that hit it), kept even where the ungapped read
+//     would leave its contig; one (diagonal, d, side) task per lane forms the mismatch words of
+//     the left and the right diagonal and walks the split point k over prefix + suffix
+//     popcounts; the hits (at most 256 per mate) are collected in LDS and the concordant
+//     pair of least key is again a wave-wide minimum
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
@@ -48,6 +58,8 @@ struct MapState {
   bool have_index = false;
   // read staging (host-resident calls)
   MapBuf s1, o1, s2, o2, r_contig, r_pos1, r_pos2, r_strand, r_mm1, r_mm2;
+  // the gapped pass: its result staging and the list of pairs to rescue
+  MapBuf r_d1, r_d2, r_k1, r_k2, r_flags, g_flag, g_slot, g_idx, g_tmp;
 };
 
 namespace {
@@ -160,6 +172,83 @@ __device__ __forceinline__ void map_unaligned(const MapPairArgs& A, int64_t pr) 
   A.mm2[pr] = 0;
 }
 
+// lane = variant * 16 + word: the read as given (strand 0) and reverse-complemented (1) as
+// bit planes in LDS, each row closed by a zero word; asc holds the two mates' ASCII bases
+__device__ __forceinline__ void map_pack_variants(const unsigned char* asc, int L1, int L2, int lane,
+                                                  uint32_t* xlo, uint32_t* xhi, uint32_t* xnn) {
+  const int v = lane >> 4, slot = lane & 15;
+  const int Lv = (v >> 1) ? L2 : L1;
+  const unsigned char* src = asc + (v >> 1) * kMapMaxRead;
+  uint32_t lo = 0, hi = 0, n = 0;
+  for (int b = 0; b < 32; ++b) {
+    const int i = slot * 32 + b;
+    if (i >= Lv) break;
+    int code = base_code((v & 1) ? src[Lv - 1 - i] : src[i]);
+    if ((v & 1) && code < 4) code = 3 - code;
+    lo |= (uint32_t)(code & 1) << b;
+    hi |= (uint32_t)((code >> 1) & 1) << b;
+    n |= (uint32_t)(code >> 2) << b;
+  }
+  xlo[v * kMapRow + slot] = lo & ~n;
+  xhi[v * kMapRow + slot] = hi & ~n;
+  xnn[v * kMapRow + slot] = n;
+  if (slot == 0) {
+    xlo[v * kMapRow + kMapWords] = 0;
+    xhi[v * kMapRow + kMapWords] = 0;
+    xnn[v * kMapRow + kMapWords] = 0;
+  }
+}
+
+// seed slot `slot` of variant v: the number of its occurrences and the first of them in the
+// sorted index (none when the slot is past the read, the seed holds an N, is absent, or
+// occurs more than max_occ times)
+__device__ __forceinline__ int map_seed_lookup(const MapIndexView& ix, int max_occ, const uint32_t* xlo,
+                                               const uint32_t* xhi, const uint32_t* xnn, int v, int slot,
+                                               int Lv, int* first) {
+  const int S = ix.S;
+  const int off = slot * S;
+  int cnt = 0;
+  if (slot < min(Lv / S, kMapSlots)) {
+    const int W = off >> 5, sh = off & 31;
+    const uint32_t mask = S == 32 ? 0xFFFFFFFFu : (1u << S) - 1u;
+    const uint32_t* r = xnn + v * kMapRow + W;
+    if ((window32(r[0], r[1], sh) & mask) == 0) {
+      const uint32_t* pl = xlo + v * kMapRow + W;
+      const uint32_t* ph = xhi + v * kMapRow + W;
+      const uint64_t key = ((uint64_t)(window32(ph[0], ph[1], sh) & mask) << S) | (window32(pl[0], pl[1], sh) & mask);
+      const uint32_t b = (uint32_t)(key >> ix.bshift);
+      int lo = (int)ix.bucket[b];
+      const int end = (int)ix.bucket[b + 1];
+      int hi = end;
+      while (lo < hi) {                                      // lower bound within the bucket
+        const int mid = (lo + hi) >> 1;
+        if (ix.keys[mid] < key) lo = mid + 1; else hi = mid;
+      }
+      *first = lo;
+      while (cnt <= max_occ && lo + cnt < end && ix.keys[lo + cnt] == key) ++cnt;
+      if (cnt > max_occ) cnt = 0;
+    }
+  }
+  return cnt;
+}
+
+// mismatches of the read word at `row` (variant * kMapRow + word) against the 32 store bases
+// from position gg on.  kGuard: gg may be as low as -32; the bases before the store are N
+template <bool kGuard>
+__device__ __forceinline__ uint32_t map_mis_word(const MapIndexView& ix, const uint32_t* xlo, const uint32_t* xhi,
+                                                 const uint32_t* xnn, int row, int gg) {
+  const int W = gg >> 5, sh = gg & 31;
+  uint2 a = make_uint2(0u, 0u);
+  uint32_t na = ~0u;
+  if (!kGuard || W >= 0) {
+    a = ix.pk[W];
+    na = ix.nm[W];
+  }
+  const uint2 b = ix.pk[W + 1];
+  return (xlo[row] ^ window32(a.x, b.x, sh)) | (xhi[row] ^ window32(a.y, b.y, sh)) | xnn[row] |
+         window32(na, ix.nm[W + 1], sh);
+}
+
 __global__ __launch_bounds__(64) void k_map_pairs(const MapPairArgs A) {
   extern __shared__ __align__(16) unsigned char map_lds[];
   const int lane = threadIdx.x;
@@ -193,54 +282,14 @@ __global__ __launch_bounds__(64) void k_map_pairs(const MapPairArgs A) {
   // lane = variant * 16 + word: the read as given (strand 0) and reverse-complemented (1)
   const int v = lane >> 4, slot = lane & 15;
   const int Lv = (v >> 1) ? L2 : L1;
-  {
-    const unsigned char* src = asc + (v >> 1) * kMapMaxRead;
-    uint32_t lo = 0, hi = 0, n = 0;
-    for (int b = 0; b < 32; ++b) {
-      const int i = slot * 32 + b;
-      if (i >= Lv) break;
-      int code = base_code((v & 1) ? src[Lv - 1 - i] : src[i]);
-      if ((v & 1) && code < 4) code = 3 - code;
-      lo |= (uint32_t)(code & 1) << b;
-      hi |= (uint32_t)((code >> 1) & 1) << b;
-      n |= (uint32_t)(code >> 2) << b;
-    }
-    xlo[v * kMapRow + slot] = lo & ~n;
-    xhi[v * kMapRow + slot] = hi & ~n;
-    xnn[v * kMapRow + slot] = n;
-    if (slot == 0) {
-      xlo[v * kMapRow + kMapWords] = 0;
-      xhi[v * kMapRow + kMapWords] = 0;
-      xnn[v * kMapRow + kMapWords] = 0;
-    }
-  }
+  map_pack_variants(asc, L1, L2, lane, xlo, xhi, xnn);
   __syncthreads();
 
   // lane = variant * 16 + seed slot: the seed's occurrences (none when it holds an N, is
   // absent, or occurs more than max_occ times)
-  int first = 0, cnt = 0;
+  int first = 0;
   const int off = slot * S;
-  if (slot < min(Lv / S, kMapSlots)) {
-    const int W = off >> 5, sh = off & 31;
-    const uint32_t mask = S == 32 ? 0xFFFFFFFFu : (1u << S) - 1u;
-    const uint32_t* r = xnn + v * kMapRow + W;
-    if ((window32(r[0], r[1], sh) & mask) == 0) {
-      const uint32_t* pl = xlo + v * kMapRow + W;
-      const uint32_t* ph = xhi + v * kMapRow + W;
-      const uint64_t key = ((uint64_t)(window32(ph[0], ph[1], sh) & mask) << S) | (window32(pl[0], pl[1], sh) & mask);
-      const uint32_t b = (uint32_t)(key >> ix.bshift);
-      int lo = (int)ix.bucket[b];
-      const int end = (int)ix.bucket[b + 1];
-      int hi = end;
-      while (lo < hi) {                                      // lower bound within the bucket
-        const int mid = (lo + hi) >> 1;
-        if (ix.keys[mid] < key) lo = mid + 1; else hi = mid;
-      }
-      first = lo;
-      while (cnt <= A.max_occ && lo + cnt < end && ix.keys[lo + cnt] == key) ++cnt;
-      if (cnt > A.max_occ) cnt = 0;
-    }
-  }
+  const int cnt = map_seed_lookup(ix, A.max_occ, xlo, xhi, xnn, v, slot, Lv, &first);
   int n_cand;
   const int start = wave_excl_scan_dpp(cnt, &n_cand);
   if (slot == 0) vst[v] = start;
@@ -272,11 +321,7 @@ __global__ __launch_bounds__(64) void k_map_pairs(const MapPairArgs A) {
     const int rem = ((uv >> 1) ? L2 : L1) - 32 * w;
     if (rem <= 0) continue;
     const int gg = ug[u] + 32 * w;                           // < the contig's end <= total
-    const int W = gg >> 5, sh = gg & 31;
-    const uint2 a = ix.pk[W], b = ix.pk[W + 1];
-    uint32_t mis = (xlo[uv * kMapRow + w] ^ window32(a.x, b.x, sh)) |
-                   (xhi[uv * kMapRow + w] ^ window32(a.y, b.y, sh)) |
-                   xnn[uv * kMapRow + w] | window32(ix.nm[W], ix.nm[W + 1], sh);
+    uint32_t mis = map_mis_word<false>(ix, xlo, xhi, xnn, uv * kMapRow + w, gg);
     if (rem < 32) mis &= (1u << rem) - 1u;
     if (mis) atomicAdd(&um[u], (uint32_t)__popc(mis));
   }
@@ -318,6 +363,241 @@ __global__ __launch_bounds__(64) void k_map_pairs(const MapPairArgs A) {
     A.strand1[pr] = (uint8_t)((um[wa] >> 16) & 1);
     A.mm1[pr] = (uint8_t)(um[wa] & 0xFFFFu);
     A.mm2[pr] = (uint8_t)(um[wb] & 0xFFFFu);
+  }
+}
+
+// ---- the single-gap rescue ------------------------------------------------------------
+
+constexpr int kMapGapMax = 8;           // max_gap
+constexpr int kMapGapHits = 256;        // hits per mate
+constexpr int kMapGapLaunch = 1 << 16;  // pairs per k_map_gap launch
+// LDS: planes, counters, the two hit lists and the ASCII reads, plus 21 bytes per entry of
+// the candidate list (64 * max_occ entries)
+constexpr int kMapGapFixedLds = (3 * 4 * kMapRow + 16) * 4 + 2 * kMapGapHits * 12 + 2 * kMapMaxRead;
+constexpr int kMapGapEntryLds = 21;
+static_assert(kMapGapMax + 8 < 32 && kMapGapMax < 32, "d + 8 is packed in 5 bits; loads reach max_gap past a contig");
+
+struct MapGapArgs {
+  MapPairArgs P;              // the index, the rule, the reads and the six result arrays
+  int max_gap, n;             // n: pairs of this launch
+  const int32_t* idx;         // [n] their pair numbers
+  int8_t* d1; int8_t* d2; int16_t* k1; int16_t* k2; uint8_t* flags;
+};
+
+__global__ void k_map_gap_flag(const MapPairArgs A, int32_t* flag) {
+  const int64_t pr = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (pr >= A.n_pairs) return;
+  flag[pr] = A.contig[pr] < 0 && A.o1[pr + 1] - A.o1[pr] >= A.ix.S && A.o2[pr + 1] - A.o2[pr] >= A.ix.S;
+}
+
+__global__ void k_map_gap_list(int64_t n, const int32_t* flag, const int32_t* slot, int32_t* idx) {
+  const int64_t pr = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (pr < n && flag[pr]) idx[slot[pr]] = (int32_t)pr;
+}
+
+// one diagonal of one variant: read index i against store position g0 + i
+struct MapDiag {
+  const MapIndexView& ix;
+  const uint32_t *xlo, *xhi, *xnn;
+  int row, L, g0;
+  // mismatch bits of read word w (bits at and past L are 0)
+  __device__ __forceinline__ uint32_t word(int w) const {
+    uint32_t mis = map_mis_word<true>(ix, xlo, xhi, xnn, row + w, g0 + 32 * w);
+    const int rem = L - 32 * w;
+    if (rem < 32) mis &= (1u << rem) - 1u;
+    return mis;
+  }
+  // mismatches among read indices [0, j), j <= L
+  __device__ __forceinline__ int prefix(int j) const {
+    int n = 0;
+    for (int w = 0; w < (j >> 5); ++w) n += __popc(word(w));
+    if (j & 31) n += __popc(word(j >> 5) & ((1u << (j & 31)) - 1u));
+    return n;
+  }
+};
+
+// One wave per listed pair.  Every store load is a word W or W + 1 of a position in
+// [p - max_gap, p + L + max_gap) with coff[c] <= p and p + L + d <= coff[c + 1]: W >= -1
+// (guarded) and W + 1 <= ceil(total / 32) + 1, the last padded word, since max_gap < 32.
+__global__ __launch_bounds__(64) void k_map_gap(const MapGapArgs G) {
+  extern __shared__ __align__(16) unsigned char map_lds[];
+  const MapPairArgs& A = G.P;
+  const int lane = threadIdx.x;
+  const int64_t pr = G.idx[blockIdx.x];
+  const MapIndexView& ix = A.ix;
+  const int S = ix.S;
+  const int cap = 64 * A.max_occ;
+  uint32_t* xlo = reinterpret_cast<uint32_t*>(map_lds);      // [4][kMapRow] variant m * 2 + s
+  uint32_t* xhi = xlo + 4 * kMapRow;
+  uint32_t* xnn = xhi + 4 * kMapRow;
+  int* vst = reinterpret_cast<int*>(xnn + 4 * kMapRow);      // [5] first entry of a variant, end
+  int* ctr = vst + 8;                                        // [0] diagonals, [1 + m] hits of mate m
+  int* hg = ctr + 8;                                         // [2][kMapGapHits] hits: start,
+  int* hc = hg + 2 * kMapGapHits;                            //   contig,
+  uint32_t* hw = reinterpret_cast<uint32_t*>(hc + 2 * kMapGapHits);  // strand, d + 8, k, mm
+  int* list = reinterpret_cast<int*>(hw + 2 * kMapGapHits);  // [cap] seed hits: diagonal,
+  int* lcon = list + cap;                                    //   contig of the occurrence
+  int* ug = lcon + cap;                                      // [cap] distinct diagonals: start,
+  int* uc = ug + cap;                                        //   contig,
+  uint32_t* um = reinterpret_cast<uint32_t*>(uc + cap);      //   variant << 16 | seed slots
+  unsigned char* asc = reinterpret_cast<unsigned char*>(um + cap);   // [2][kMapMaxRead]
+  unsigned char* lln = asc + 2 * kMapMaxRead;                // [cap] seed hits: the lane
+
+  const int64_t b1 = A.o1[pr], b2 = A.o2[pr];
+  const int L1 = (int)(A.o1[pr + 1] - b1), L2 = (int)(A.o2[pr + 1] - b2);   // S..512: listed
+  for (int i = lane; i < L1; i += 64) asc[i] = (unsigned char)A.s1[b1 + i];
+  for (int i = lane; i < L2; i += 64) asc[kMapMaxRead + i] = (unsigned char)A.s2[b2 + i];
+  if (lane < 3) ctr[lane] = 0;
+  __syncthreads();
+  const int v = lane >> 4, slot = lane & 15;
+  const int Lv = (v >> 1) ? L2 : L1;
+  map_pack_variants(asc, L1, L2, lane, xlo, xhi, xnn);
+  __syncthreads();
+
+  // lane = variant * 16 + seed slot: every occurrence with its diagonal and its own contig
+  int first = 0;
+  const int off = slot * S;
+  const int cnt = map_seed_lookup(ix, A.max_occ, xlo, xhi, xnn, v, slot, Lv, &first);
+  int n_cand;
+  const int start = wave_excl_scan_dpp(cnt, &n_cand);
+  if (slot == 0) vst[v] = start;
+  if (lane == 0) vst[4] = n_cand;
+  for (int k = 0; k < cnt; ++k) {
+    const int q = ix.kpos[first + k];
+    list[start + k] = q - off;
+    lcon[start + k] = contig_of(ix.coff, ix.n_contigs, q);
+    lln[start + k] = (unsigned char)lane;
+  }
+  __syncthreads();
+
+  // distinct (variant, diagonal, contig), each with the seed slots that hit it; nothing is
+  // dropped here: a diagonal that leaves its contig can still be one side of a gap
+  for (int e = lane; e < n_cand; e += 64) {
+    const int g = list[e], c = lcon[e];
+    const int ev = lln[e] >> 4;
+    bool dup = false;
+    uint32_t slots = 0;
+    for (int k = vst[ev]; k < vst[ev + 1] && !dup; ++k) {
+      if (list[k] != g || lcon[k] != c) continue;
+      dup = k < e;
+      slots |= 1u << (lln[k] & 15);
+    }
+    if (dup) continue;
+    const int u = atomicAdd(&ctr[0], 1);
+    ug[u] = g;
+    uc[u] = c;
+    um[u] = (uint32_t)ev << 16 | slots;
+  }
+  __syncthreads();
+  const int U = ctr[0];
+
+  // one (diagonal u, d, side) task per lane and turn.  Side 0: u is the left diagonal, the
+  // alignment starts at p = ug[u]; side 1: u is the right diagonal, p = ug[u] - d, and the
+  // task is left to side 0 of the diagonal at p when that one is listed (counted once).
+  const int nd = 2 * G.max_gap + 1;
+  for (int t = lane; t < U * 2 * nd; t += 64) {
+    const int u = t / (2 * nd), r = t - u * 2 * nd;
+    const int side = r >= nd;
+    const int d = r - side * nd - G.max_gap;
+    if (d == 0 && side) continue;
+    const uint32_t mu = um[u];
+    const int uv = (int)(mu >> 16), c = uc[u];
+    const int L = (uv >> 1) ? L2 : L1;
+    const int gap = d < 0 ? -d : 0;
+    const int klo = S, khi = L - S - gap;                    // both segments >= S
+    if (d != 0 && khi < klo) continue;
+    const int p = side ? ug[u] - d : ug[u];
+    if (p < ix.coff[c] || p + L + d > ix.coff[c + 1]) continue;
+    uint32_t sl = side ? 0u : (mu & 0xFFFFu), sr = side ? (mu & 0xFFFFu) : 0u;
+    if (d != 0) {                                            // the other diagonal's seed slots
+      const int og = side ? p : p + d;
+      uint32_t other = 0;
+      bool found = false;
+      for (int j = 0; j < U && !found; ++j)
+        if (ug[j] == og && uc[j] == c && (int)(um[j] >> 16) == uv) { found = true; other = um[j] & 0xFFFFu; }
+      if (side && found) continue;
+      if (!side) sr = other;
+    }
+    const MapDiag dl{ix, xlo, xhi, xnn, uv * kMapRow, L, p};
+    int best = 1 << 20, bk = 0;
+    if (d == 0) {
+      best = dl.prefix(L);
+    } else {
+      // seeded k: a left seed slot j needs (j + 1) S <= k, a right one j S >= k + gap, so
+      // the seeded k are [kl, khi] united with [klo, kr]
+      const int kl = sl ? (__ffs((int)sl) - 1) * S + S : (1 << 20);
+      const int kr = sr ? (31 - __clz((int)sr)) * S - gap : -1;
+      if (kl > khi && kr < klo) continue;
+      const MapDiag dr{ix, xlo, xhi, xnn, uv * kMapRow, L, p + d};
+      const int tr = dr.prefix(L);
+      int pl = dl.prefix(klo), pj = dr.prefix(klo + gap);
+      uint32_t wl = dl.word(klo >> 5), wr = dr.word((klo + gap) >> 5);
+      for (int k = klo;; ++k) {
+        const int mm = pl + tr - pj;
+        if ((k >= kl || k <= kr) && mm < best) { best = mm; bk = k; }   // the least k stays
+        if (k == khi) break;
+        const int j = k + gap;
+        pl += (int)((wl >> (k & 31)) & 1u);
+        pj += (int)((wr >> (j & 31)) & 1u);
+        if (((k + 1) & 31) == 0) wl = dl.word((k + 1) >> 5);
+        if (((j + 1) & 31) == 0) wr = dr.word((j + 1) >> 5);
+      }
+    }
+    if (best > A.max_mm) continue;
+    const int m = uv >> 1;
+    const int h = atomicAdd(&ctr[1 + m], 1);
+    if (h >= kMapGapHits) continue;
+    hg[m * kMapGapHits + h] = p;
+    hc[m * kMapGapHits + h] = c;
+    hw[m * kMapGapHits + h] = (uint32_t)(uv & 1) << 24 | (uint32_t)(d + 8) << 16 | (uint32_t)bk << 6 | (uint32_t)best;
+  }
+  __syncthreads();
+  const int n1 = ctr[1], n2 = ctr[2];
+  if (n1 > kMapGapHits || n2 > kMapGapHits) {                // the pair stays unaligned
+    if (lane == 0) G.flags[pr] = 2;
+    return;
+  }
+
+  // the concordant pair of least (nm1 + nm2, |d1| + |d2|, contig, f.p, fragment, strand of
+  // mate 1, d1, d2)
+  uint64_t khi = ~0ull, klo = ~0ull;
+  int wa = 0, wb = 0;
+  for (int t = lane; t < n1 * n2; t += 64) {
+    const int a = t / n2, b = kMapGapHits + t - a * n2;
+    const uint32_t ha = hw[a], hb = hw[b];
+    if (((ha ^ hb) >> 24) == 0 || hc[a] != hc[b]) continue;
+    const int da = (int)((ha >> 16) & 31u) - 8, db = (int)((hb >> 16) & 31u) - 8;
+    const bool afirst = (ha >> 24) == 0;                     // mate 1 is the + mate
+    const int64_t gf = afirst ? hg[a] : hg[b], gr = afirst ? hg[b] : hg[a];
+    const int64_t ef = gf + (afirst ? L1 + da : L2 + db), er = gr + (afirst ? L2 + db : L1 + da);
+    if (gf > gr || ef > er) continue;                        // dovetail
+    const int64_t frag = er - gf;
+    if (frag < A.min_ins || frag > A.max_ins) continue;
+    const int ad = (da < 0 ? -da : da) + (db < 0 ? -db : db);
+    const int nm = (int)(ha & 63u) + (int)(hb & 63u) + ad;
+    const uint64_t h = ((uint64_t)nm << 40) | ((uint64_t)ad << 32) | (uint64_t)gf;
+    const uint64_t l = ((uint64_t)frag << 11) | (uint64_t)(ha >> 24) << 10 | (uint64_t)(da + 8) << 5 |
+                       (uint64_t)(db + 8);
+    if (h < khi || (h == khi && l < klo)) { khi = h; klo = l; wa = a; wb = b; }
+  }
+  const uint64_t bhi = wave_butterfly(khi, [](uint64_t x, uint64_t y) { return x < y ? x : y; });
+  const uint64_t mlo = khi == bhi ? klo : ~0ull;
+  const uint64_t blo = wave_butterfly(mlo, [](uint64_t x, uint64_t y) { return x < y ? x : y; });
+  if (bhi == ~0ull) return;                                  // unaligned, as k_map_pairs left it
+  if (khi == bhi && klo == blo) {                            // the key is unique: one lane
+    const int c = hc[wa];
+    const uint32_t ha = hw[wa], hb = hw[wb];
+    A.contig[pr] = c;
+    A.pos1[pr] = hg[wa] - ix.coff[c] + 1;
+    A.pos2[pr] = hg[wb] - ix.coff[c] + 1;
+    A.strand1[pr] = (uint8_t)(ha >> 24);
+    A.mm1[pr] = (uint8_t)(ha & 63u);
+    A.mm2[pr] = (uint8_t)(hb & 63u);
+    G.d1[pr] = (int8_t)((int)((ha >> 16) & 31u) - 8);
+    G.d2[pr] = (int8_t)((int)((hb >> 16) & 31u) - 8);
+    G.k1[pr] = (int16_t)((ha >> 6) & 1023u);
+    G.k2[pr] = (int16_t)((hb >> 6) & 1023u);
+    G.flags[pr] = 1;
   }
 }
 
@@ -366,6 +646,46 @@ MapIndexView map_view(const MapState* st) {
     if ((rc = (x))) goto done; \
   } while (0)
 
+// The gapped pass over the results k_map_pairs has written: list the pairs to rescue on the
+// device, then k_map_gap in launches of at most kMapGapLaunch pairs.
+int map_rescue(MapState* st, MapGapArgs GA, hipStream_t s, std::string* err) {
+  const int64_t NP = GA.P.n_pairs;
+  int rc = 0;
+  int32_t last_flag = 0, last_slot = 0;
+  size_t tmp_bytes = 0;
+  int32_t *flag, *slot;
+  int64_t n = 0;
+  const size_t lds = (size_t)kMapGapFixedLds + (size_t)kMapGapEntryLds * 64 * (size_t)GA.P.max_occ;
+  MAP_RC(map_ensure(st->g_flag, sizeof(int32_t) * NP, err));
+  MAP_RC(map_ensure(st->g_slot, sizeof(int32_t) * NP, err));
+  MAP_RC(map_ensure(st->g_idx, sizeof(int32_t) * NP, err));
+  flag = static_cast<int32_t*>(st->g_flag.p);
+  slot = static_cast<int32_t*>(st->g_slot.p);
+  hipLaunchKernelGGL(k_map_gap_flag, dim3((unsigned)((NP + 255) / 256)), dim3(256), 0, s, GA.P, flag);
+  MAP_TRY(hipGetLastError());
+  MAP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, flag, slot, (int)NP, s));
+  MAP_RC(map_ensure(st->g_tmp, tmp_bytes, err));
+  MAP_TRY(hipcub::DeviceScan::ExclusiveSum(st->g_tmp.p, tmp_bytes, flag, slot, (int)NP, s));
+  hipLaunchKernelGGL(k_map_gap_list, dim3((unsigned)((NP + 255) / 256)), dim3(256), 0, s, NP, flag, slot,
+                     static_cast<int32_t*>(st->g_idx.p));
+  MAP_TRY(hipGetLastError());
+  MAP_TRY(hipMemcpyAsync(&last_flag, flag + (NP - 1), sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  MAP_TRY(hipMemcpyAsync(&last_slot, slot + (NP - 1), sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  MAP_TRY(hipStreamSynchronize(s));
+  n = (int64_t)last_flag + last_slot;
+  if (n == 0) return 0;
+  MAP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_map_gap),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  for (int64_t lo = 0; lo < n; lo += kMapGapLaunch) {
+    GA.n = (int)std::min<int64_t>(kMapGapLaunch, n - lo);
+    GA.idx = static_cast<const int32_t*>(st->g_idx.p) + lo;
+    hipLaunchKernelGGL(k_map_gap, dim3((unsigned)GA.n), dim3(64), lds, s, GA);
+    MAP_TRY(hipGetLastError());
+  }
+done:
+  return rc;
+}
+
 }  // namespace
 
 MapState* map_create() { return new MapState(); }
@@ -374,7 +694,8 @@ void map_destroy(MapState* st) {
   if (!st) return;
   MapBuf* bufs[] = {&st->pk, &st->nm, &st->coff, &st->keys, &st->kpos, &st->bucket, &st->s1, &st->o1,
                     &st->s2, &st->o2, &st->r_contig, &st->r_pos1, &st->r_pos2, &st->r_strand, &st->r_mm1,
-                    &st->r_mm2};
+                    &st->r_mm2, &st->r_d1, &st->r_d2, &st->r_k1, &st->r_k2, &st->r_flags, &st->g_flag,
+                    &st->g_slot, &st->g_idx, &st->g_tmp};
   for (MapBuf* b : bufs) map_release(*b);
   delete st;
 }
@@ -479,9 +800,13 @@ done:
   return rc;
 }
 
-int map_pairs(MapState* st, const MapReads& rd, const MapRule& rule, const MapOut& out, hipStream_t s,
-              std::string* err) {
+namespace {
+
+// map_pairs; with gout, also the gap fields (zeroed) and, for max_gap > 0, the rescue pass
+int map_pairs_run(MapState* st, const MapReads& rd, const MapRule& rule, const MapOut& out, int max_gap,
+                  const MapGapOut* gout, hipStream_t s, std::string* err) {
   const int64_t NP = rd.n_pairs;
+  MapGapArgs GA{};
   int rc = 0;
   std::vector<int64_t> h1, h2;
   const int64_t *o1 = rd.off1, *o2 = rd.off2;
@@ -545,6 +870,28 @@ int map_pairs(MapState* st, const MapReads& rd, const MapRule& rule, const MapOu
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(k_map_pairs, dim3((unsigned)NP), dim3(64), lds, s, A);
   MAP_TRY(hipGetLastError());
+  if (gout) {
+    GA.P = A;
+    GA.max_gap = max_gap;
+    if (rd.device_resident) {
+      GA.d1 = gout->d1; GA.d2 = gout->d2; GA.k1 = gout->k1; GA.k2 = gout->k2; GA.flags = gout->flags;
+    } else {
+      MAP_RC(map_ensure(st->r_d1, (size_t)NP, err));
+      MAP_RC(map_ensure(st->r_d2, (size_t)NP, err));
+      MAP_RC(map_ensure(st->r_k1, sizeof(int16_t) * NP, err));
+      MAP_RC(map_ensure(st->r_k2, sizeof(int16_t) * NP, err));
+      MAP_RC(map_ensure(st->r_flags, (size_t)NP, err));
+      GA.d1 = static_cast<int8_t*>(st->r_d1.p); GA.d2 = static_cast<int8_t*>(st->r_d2.p);
+      GA.k1 = static_cast<int16_t*>(st->r_k1.p); GA.k2 = static_cast<int16_t*>(st->r_k2.p);
+      GA.flags = static_cast<uint8_t*>(st->r_flags.p);
+    }
+    MAP_TRY(hipMemsetAsync(GA.d1, 0, (size_t)NP, s));
+    MAP_TRY(hipMemsetAsync(GA.d2, 0, (size_t)NP, s));
+    MAP_TRY(hipMemsetAsync(GA.k1, 0, sizeof(int16_t) * NP, s));
+    MAP_TRY(hipMemsetAsync(GA.k2, 0, sizeof(int16_t) * NP, s));
+    MAP_TRY(hipMemsetAsync(GA.flags, 0, (size_t)NP, s));
+    if (max_gap > 0) MAP_RC(map_rescue(st, GA, s, err));
+  }
   if (!rd.device_resident) {
     MAP_TRY(hipMemcpyAsync(out.contig, A.contig, sizeof(int32_t) * NP, hipMemcpyDeviceToHost, s));
     MAP_TRY(hipMemcpyAsync(out.pos1, A.pos1, sizeof(int32_t) * NP, hipMemcpyDeviceToHost, s));
@@ -552,10 +899,31 @@ int map_pairs(MapState* st, const MapReads& rd, const MapRule& rule, const MapOu
     MAP_TRY(hipMemcpyAsync(out.strand1, A.strand1, (size_t)NP, hipMemcpyDeviceToHost, s));
     MAP_TRY(hipMemcpyAsync(out.mm1, A.mm1, (size_t)NP, hipMemcpyDeviceToHost, s));
     MAP_TRY(hipMemcpyAsync(out.mm2, A.mm2, (size_t)NP, hipMemcpyDeviceToHost, s));
+    if (gout) {
+      MAP_TRY(hipMemcpyAsync(gout->d1, GA.d1, (size_t)NP, hipMemcpyDeviceToHost, s));
+      MAP_TRY(hipMemcpyAsync(gout->d2, GA.d2, (size_t)NP, hipMemcpyDeviceToHost, s));
+      MAP_TRY(hipMemcpyAsync(gout->k1, GA.k1, sizeof(int16_t) * NP, hipMemcpyDeviceToHost, s));
+      MAP_TRY(hipMemcpyAsync(gout->k2, GA.k2, sizeof(int16_t) * NP, hipMemcpyDeviceToHost, s));
+      MAP_TRY(hipMemcpyAsync(gout->flags, GA.flags, (size_t)NP, hipMemcpyDeviceToHost, s));
+    }
+    MAP_TRY(hipStreamSynchronize(s));
+  } else if (gout) {
     MAP_TRY(hipStreamSynchronize(s));
   }
 done:
   return rc;
+}
+
+}  // namespace
+
+int map_pairs(MapState* st, const MapReads& rd, const MapRule& rule, const MapOut& out, hipStream_t s,
+              std::string* err) {
+  return map_pairs_run(st, rd, rule, out, 0, nullptr, s, err);
+}
+
+int map_pairs_gapped(MapState* st, const MapReads& rd, const MapRule& rule, int max_gap, const MapOut& out,
+                     const MapGapOut& gout, hipStream_t s, std::string* err) {
+  return map_pairs_run(st, rd, rule, out, max_gap, &gout, s, err);
 }
 
 }  // namespace wf

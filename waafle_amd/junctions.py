@@ -361,7 +361,7 @@ def build_parser():
     g = ap.add_argument_group("read mapper")
     g.add_argument("--mapper", choices=["bowtie2", "native"], default="bowtie2",
                    help="how --reads1/--reads2 are aligned: bowtie2 (as upstream), or the built-in\n"
-                        "ungapped seed-and-verify mapper on the GPU (not a bowtie2 clone)\n"
+                        "ungapped seed-and-verify mapper on the GPU (not a bowtie2 clone; see --max-gap)\n"
                         "[default: bowtie2]")
     g.add_argument("--seed-length", type=int, default=20, metavar="<int>",
                    help="native mapper: seed length, 12..32\n[default: 20]")
@@ -373,6 +373,9 @@ def build_parser():
                    help="native mapper: minimum fragment length\n[default: 0]")
     g.add_argument("--max-insert", type=int, default=500, metavar="<int>",
                    help="native mapper: maximum fragment length\n[default: 500]")
+    g.add_argument("--max-gap", type=int, default=0, metavar="<int>",
+                   help="native mapper: pairs left unaligned are tried again with at most one\n"
+                        "insertion or deletion of up to this many bases per mate, 0..8 (0: off)\n[default: 0]")
     return ap
 
 
@@ -397,7 +400,7 @@ def _native_map(args, p_sam):
     pairs, total = mapper.map_pairs(contigs, args.reads1, args.reads2, sam_path=p_sam, device=args.gpu,
                                     seed_length=args.seed_length, max_seed_hits=args.max_seed_hits,
                                     max_mismatches=args.max_mismatches, min_insert=args.min_insert,
-                                    max_insert=args.max_insert)
+                                    max_insert=args.max_insert, max_gap=args.max_gap)
     inputs.say("Aligned {} of {} read pairs.".format(len(pairs[0]), total))
     return pairs + ([],)
 

@@ -118,6 +118,14 @@ class WfMapResult(C.Structure):
                 ("mm2", _P)]
 
 
+class WfMapGapParams(C.Structure):
+    _fields_ = [("max_gap", C.c_int32), ("_pad", C.c_int32 * 3)]
+
+
+class WfMapGapResult(C.Structure):
+    _fields_ = [("d1", _P), ("d2", _P), ("k1", _P), ("k2", _P), ("flags", _P)]
+
+
 class WfDetails(C.Structure):
     _fields_ = [("n_evals", C.c_int64), ("eval_contig", _P), ("eval_level", _P),
                 ("n_segs", C.c_int64), ("seg_level", _P), ("seg_contig", _P), ("seg_clade", _P),
@@ -150,6 +158,9 @@ SIGNATURES = {
     "wf_map_index": (C.c_int, [C.c_void_p, C.POINTER(WfMapContigs), C.POINTER(WfMapParams)]),
     "wf_map_pairs": (C.c_int, [C.c_void_p, C.POINTER(WfMapReads), C.POINTER(WfMapParams),
                                C.POINTER(WfMapResult)]),
+    "wf_map_pairs_gapped": (C.c_int, [C.c_void_p, C.POINTER(WfMapReads), C.POINTER(WfMapParams),
+                                      C.POINTER(WfMapGapParams), C.POINTER(WfMapResult),
+                                      C.POINTER(WfMapGapResult)]),
     "wf_details_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "wf_details_read": (C.c_int, [C.c_void_p, C.POINTER(WfDetails)]),
 }

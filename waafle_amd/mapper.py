@@ -2,7 +2,9 @@
 
 A deterministic seed-and-verify ungapped mapper (DESIGN.md §11 states the rule): enough for
 waafle_junctions, which only uses each mate's RNAME, POS and POS + cigar_length - 1.  It is
-not a bowtie2 clone: no gapped alignments, no soft clipping, no MAPQ, no random tie-breaks.
+not a bowtie2 clone: no affine-gap alignments, no soft clipping, no MAPQ, no random
+tie-breaks.  With max_gap > 0 the pairs left unaligned get a second pass in which each mate
+may carry one insertion or deletion of at most max_gap bases (wf_map_pairs_gapped).
 
 Host side (this module): the FASTA sequence reader, the paired FASTQ reader (4-line records,
 plain or .gz, streamed in blocks), the calls into wf_map_index / wf_map_pairs and the SAM
@@ -155,13 +157,21 @@ def iter_fastq_pairs(path1, path2, chunk=CHUNK_PAIRS):
 
 RESULT_FIELDS = (("contig", np.int32), ("pos1", np.int32), ("pos2", np.int32),
                  ("strand1", np.uint8), ("mm1", np.uint8), ("mm2", np.uint8))
+# the gapped pass: d > 0 deletion, d < 0 insertion after the mate's first k bases (counted
+# along the contig); flags bit 0: aligned by the gapped pass, bit 1: hit-list overflow
+GAP_FIELDS = (("d1", np.int8), ("d2", np.int8), ("k1", np.int16), ("k2", np.int16), ("flags", np.uint8))
+MAX_GAP = 8
 
 
 class Mapper:
-    """One context with the index of one contig set (wf_map_index); `map` runs wf_map_pairs."""
+    """One context with the index of one contig set (wf_map_index); `map` runs wf_map_pairs
+    or, with max_gap > 0, wf_map_pairs_gapped."""
 
     def __init__(self, seq, off, seed_length=20, max_seed_hits=16, max_mismatches=4, min_insert=0,
-                 max_insert=500, device=0):
+                 max_insert=500, device=0, max_gap=0):
+        if not 0 <= int(max_gap) <= MAX_GAP:
+            raise MapperError("max_gap {} outside 0..{}".format(max_gap, MAX_GAP))
+        self.gap_params = L.WfMapGapParams(max_gap=int(max_gap))
         self.so = L.load()
         self.h = C.c_void_p()
         rc = self.so.wf_init(int(device), C.byref(self.h))
@@ -187,28 +197,45 @@ class Mapper:
         c = L.WfMapContigs(n_contigs=len(off) - 1, seq=L.ptr(seq), off=L.ptr(off))
         self._check(self.so.wf_map_index(self.h, C.byref(c), C.byref(self.params)))
 
-    def map(self, seq1, off1, seq2, off2, params=None):
-        """Result arrays (RESULT_FIELDS) for the pairs given as host arrays."""
+    def map(self, seq1, off1, seq2, off2, params=None, gapped=None):
+        """Result arrays (RESULT_FIELDS and GAP_FIELDS) for the pairs given as host arrays.
+        gapped: call wf_map_pairs_gapped (default: when max_gap > 0; with max_gap 0 the gap
+        fields are zeros either way, and wf_map_pairs spares their copies)."""
         seq1, seq2 = (np.ascontiguousarray(s, dtype=np.uint8) for s in (seq1, seq2))
         off1, off2 = (np.ascontiguousarray(o, dtype=np.int64) for o in (off1, off2))
         n = len(off1) - 1
         if len(off2) - 1 != n:
             raise MapperError("mate arrays of different lengths")
-        out = {f: np.zeros(n, dt) for f, dt in RESULT_FIELDS}
+        out = {f: np.zeros(n, dt) for f, dt in RESULT_FIELDS + GAP_FIELDS}
         rd = L.WfMapReads(n_pairs=n, device_resident=0, seq1=L.ptr(seq1), off1=L.ptr(off1),
                           seq2=L.ptr(seq2), off2=L.ptr(off2))
         r = L.WfMapResult(**{f: L.ptr(out[f]) for f, _ in RESULT_FIELDS})
-        self._check(self.so.wf_map_pairs(self.h, C.byref(rd), C.byref(params or self.params), C.byref(r)))
+        if gapped is None:
+            gapped = self.gap_params.max_gap != 0
+        if gapped:
+            g = L.WfMapGapResult(**{f: L.ptr(out[f]) for f, _ in GAP_FIELDS})
+            self._check(self.so.wf_map_pairs_gapped(self.h, C.byref(rd), C.byref(params or self.params),
+                                                    C.byref(self.gap_params), C.byref(r), C.byref(g)))
+        else:
+            self._check(self.so.wf_map_pairs(self.h, C.byref(rd), C.byref(params or self.params), C.byref(r)))
         return out
 
     def map_device(self, n_pairs, seq1, off1, seq2, off2, out):
         """Device-resident form: device addresses (ints, e.g. a tensor's data_ptr()) of the
         uint8 bases and int64 offsets on this context's device; `out` maps each of
-        RESULT_FIELDS to the address of its array.  Returns after the work is done."""
+        RESULT_FIELDS, and of GAP_FIELDS (which may be left out when max_gap is 0), to the
+        address of its array.  Returns after the work is done."""
         rd = L.WfMapReads(n_pairs=int(n_pairs), device_resident=1, seq1=seq1, off1=off1, seq2=seq2,
                           off2=off2)
         r = L.WfMapResult(**{f: out[f] for f, _ in RESULT_FIELDS})
-        self._check(self.so.wf_map_pairs(self.h, C.byref(rd), C.byref(self.params), C.byref(r)))
+        if all(f in out for f, _ in GAP_FIELDS):
+            g = L.WfMapGapResult(**{f: out[f] for f, _ in GAP_FIELDS})
+            self._check(self.so.wf_map_pairs_gapped(self.h, C.byref(rd), C.byref(self.params),
+                                                    C.byref(self.gap_params), C.byref(r), C.byref(g)))
+        elif self.gap_params.max_gap:
+            raise MapperError("max_gap > 0 needs the arrays of GAP_FIELDS in `out`")
+        else:
+            self._check(self.so.wf_map_pairs(self.h, C.byref(rd), C.byref(self.params), C.byref(r)))
         self._check(self.so.wf_synchronize(self.h))
 
     def close(self):
@@ -234,12 +261,24 @@ def sam_header(names, lengths):
     return lines
 
 
+def _cigar(length, d, k):
+    if d > 0:
+        return "{}M{}D{}M".format(k, d, length - k)
+    if d < 0:
+        return "{}M{}I{}M".format(k, -d, length - k + d)
+    return "{}M".format(length)
+
+
 def sam_records(qnames, len1, len2, res, contig_names):
     """Two records per pair: 99/147 (mate 1 on +) or 83/163 (mate 1 on -) with CIGAR <L>M and
-    NM:i:<mm>, or 77/141 when the pair is unaligned."""
+    NM:i:<mm>, or 77/141 when the pair is unaligned.  With the gap fields in `res`, a mate
+    with a gap has CIGAR <k>M<d>D<L-k>M or <k>M<g>I<L-k-g>M and NM:i:<mm + |d|>, and TLEN
+    counts the contig bases the mates span (L + d each)."""
     out = []
+    n = len(qnames)
     contig, pos1, pos2 = res["contig"].tolist(), res["pos1"].tolist(), res["pos2"].tolist()
     strand1, mm1, mm2 = res["strand1"].tolist(), res["mm1"].tolist(), res["mm2"].tolist()
+    d1, d2, k1, k2 = (res[f].tolist() if f in res else [0] * n for f in ("d1", "d2", "k1", "k2"))
     for i, q in enumerate(qnames):
         c = contig[i]
         if c < 0:
@@ -248,25 +287,28 @@ def sam_records(qnames, len1, len2, res, contig_names):
             continue
         p1, p2, l1, l2 = pos1[i], pos2[i], int(len1[i]), int(len2[i])
         if strand1[i] == 0:
-            f1, f2, frag = 99, 147, p2 + l2 - p1
+            f1, f2, frag = 99, 147, p2 + l2 + d2[i] - p1
             t1, t2 = frag, -frag
         else:
-            f1, f2, frag = 83, 163, p1 + l1 - p2
+            f1, f2, frag = 83, 163, p1 + l1 + d1[i] - p2
             t1, t2 = -frag, frag
         name = contig_names[c]
-        out.append("{}\t{}\t{}\t{}\t255\t{}M\t=\t{}\t{}\t*\t*\tNM:i:{}".format(
-            q, f1, name, p1, l1, p2, t1, mm1[i]))
-        out.append("{}\t{}\t{}\t{}\t255\t{}M\t=\t{}\t{}\t*\t*\tNM:i:{}".format(
-            q, f2, name, p2, l2, p1, t2, mm2[i]))
+        out.append("{}\t{}\t{}\t{}\t255\t{}\t=\t{}\t{}\t*\t*\tNM:i:{}".format(
+            q, f1, name, p1, _cigar(l1, d1[i], k1[i]), p2, t1, mm1[i] + abs(d1[i])))
+        out.append("{}\t{}\t{}\t{}\t255\t{}\t=\t{}\t{}\t*\t*\tNM:i:{}".format(
+            q, f2, name, p2, _cigar(l2, d2[i], k2[i]), p1, t2, mm2[i] + abs(d2[i])))
     return out
 
 
 def pair_arrays(res, len1, len2):
     """The aligned pairs as junctions.read_pairs returns them: (pair_contig, m1_start,
-    m1_end, m2_start, m2_end)."""
+    m1_end, m2_start, m2_end); a mate with a gap d ends at p + L + d - 1."""
     keep = res["contig"] >= 0
     p1, p2 = res["pos1"][keep].astype(np.int64), res["pos2"][keep].astype(np.int64)
     l1, l2 = np.asarray(len1, np.int64)[keep], np.asarray(len2, np.int64)[keep]
+    if "d1" in res:
+        l1 = l1 + res["d1"][keep].astype(np.int64)
+        l2 = l2 + res["d2"][keep].astype(np.int64)
     return res["contig"][keep].astype(np.int32), p1, p1 + l1 - 1, p2, p2 + l2 - 1
 
 
