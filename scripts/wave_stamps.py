@@ -67,9 +67,9 @@ def main():
     st = (C.c_ulonglong * 48)()
     so.wf_stamps_read_fast(st, 48)
     v = [int(x) for x in st]
-    sp = (C.c_ulonglong * 16)()
+    sp = (C.c_ulonglong * 32)()
     so.wf_stamps_read_sparse.argtypes = [C.POINTER(C.c_ulonglong), C.c_int]
-    so.wf_stamps_read_sparse(sp, 16)
+    so.wf_stamps_read_sparse(sp, 32)
     w = [int(x) for x in sp]
     tot = sum(v[:16]) + sum(v[32:36])                # (the explain_one laps are their own)
     nc = max(1, v[16])
@@ -87,9 +87,15 @@ def main():
                       "cycles_per_contig": sum(w[:6]) / max(1, w[8]),
                       "phases": {k: w[i] / max(1, w[8]) for i, k in enumerate(
                           ["table + loci loads", "run heads / potentials", "candidate pairs",
-                           "members' parents + sister masks", "pass 1 ranks", "pass 2, eval_two, meld, record"])},
+                           "members' parents + sister masks", "pass 1: pairs evaluated, best",
+                           "pass 2 (--range), meld, record"])},
                       "per_contig": {"segments": w[9] / max(1, w[8]), "potential clades": w[10] / max(1, w[8]),
-                                     "candidate pairs": w[11] / max(1, w[8])}}}
+                                     "candidate pairs": w[11] / max(1, w[8])},
+                      # calls by their number of candidate pairs, and those the
+                      # wave-cooperative form took (nc <= kE2WavePairs)
+                      "candidate_pairs_hist": dict(
+                          [("0", w[25])] + [(str(k), w[15 + k]) for k in range(1, 9)] + [(">8", w[24])]),
+                      "wave_form_calls": w[26]}}
     tr = (C.c_ulonglong * 16)()
     so.wf_stamps_read_triage.argtypes = [C.POINTER(C.c_ulonglong), C.c_int]
     so.wf_stamps_read_triage(tr, 16)

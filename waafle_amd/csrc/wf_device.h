@@ -478,6 +478,11 @@ constexpr int kThreadLeaves = 32;
 // explain_two from the wave form's compact hand-over (wf_fast.hip, sp_two in wf_sparse.h)
 constexpr int kE2Seg = 320;        // segments of one compact table (LDS of k_dump_sparse)
 constexpr int kE2MaxG = 63;        // loci (locus masks keep bit 63 for the root flag)
+#ifndef WF_E2_WAVE_PAIRS
+#define WF_E2_WAVE_PAIRS 8         // (-D for sweeps)
+#endif
+constexpr int kE2WavePairs = WF_E2_WAVE_PAIRS;   // candidate pairs up to which sp_two puts the
+                                                 // whole wave on each pair (else a lane a pair)
 constexpr int kPruneMax = 64;      // attachments scanned for whole-locus domination
 
 // Bounds of a segment's mean from its envelope's integral (the first wave form's pruning).

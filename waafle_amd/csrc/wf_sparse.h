@@ -1023,68 +1023,37 @@ __device__ __forceinline__ double e2_at(const E2Shared& sh, int t, uint64_t pres
   return ((pres >> g) & 1ull) ? sh.v[t + __popcll(pres & ((1ull << g) - 1ull))] : 0.0;
 }
 
-// Contig.score(c1, c2) rank (orgscorer.py:447-461): numpy-order mean over the unmasked loci
-// of the per-locus max (sp_pair_rank's arithmetic)
-__device__ __forceinline__ double e2_rank(const E2Shared& sh, int a, int b, uint64_t um, int Gu) {
-  const int ta = sh.t[a], tb = sh.t[b];
-  const uint64_t pa = sh.pres[a], pb = sh.pres[b];
-  uint64_t m = um;
-  auto next = [&]() -> double {
-    const int g = __builtin_ctzll(m);
-    m &= m - 1;
-    const double x = e2_at(sh, ta, pa, g), y = e2_at(sh, tb, pb, g);
-    return x < y ? y : x;
-  };
-  return (0.0 + np_sum_seq(Gu, next)) / (double)Gu;
-}
-
+// Everything explain_two reads from the rows of potential clades a < b, from one evaluation
+// (e2_pair: a lane's own pair; e2_pair_wave: the whole wave on one pair):
+//   rank  Contig.score(c1, c2) (orgscorer.py:447-461): numpy-order mean over the unmasked
+//         loci of the per-locus max (sp_pair_rank's arithmetic);
+//   crit  the minimum of those maxima (sp_pair_crit);
+//   the rest: set_synteny_two + apply_lgt_checks (:511-545, 678-744), sp_eval_two's arithmetic
 struct E2Eval {
-  int ok, swapped, dir;
+  double rank, crit;
+  unsigned ok : 1, swapped : 1, dir : 1;     // (one register: a lane keeps its pair's E2Eval)
   uint64_t mm, mA, mB;                       // synteny '*', 'A', 'B' after the swap
 };
 
-// set_synteny_two + apply_lgt_checks (orgscorer.py:511-545, 678-744) for potential clades
-// a < b: sp_eval_two's arithmetic
-__device__ __forceinline__ E2Eval e2_eval(const KArgs& K, const E2Shared& sh, int a, int b, uint64_t um) {
+// The swap, the direction and the LGT checks from the pair's synteny before the swap (mm,
+// ma, mb: disjoint subsets of um) and the lengths of its annotated / '*' loci.
+__device__ __forceinline__ void e2_checks(const KArgs& K, const E2Shared& sh, int a, int b, uint64_t um,
+                                          uint64_t mm, uint64_t ma, uint64_t mb, int64_t tot, int64_t amb,
+                                          E2Eval& e) {
   const DevParams& P = K.p;
-  const bool unk = sh.cl[a] == K.unknown || sh.cl[b] == K.unknown;
-  uint64_t mm = 0, ma = 0, mb = 0;
-  {
-    const int ta = sh.t[a], tb = sh.t[b];
-    const uint64_t pa = sh.pres[a], pb = sh.pres[b];
-    for (uint64_t r = um; r; r &= r - 1) {
-      const int g = __builtin_ctzll(r);
-      const uint64_t bit = 1ull << g;
-      const double s1 = e2_at(sh, ta, pa, g), s2 = e2_at(sh, tb, pb, g);
-      const double mn = s2 < s1 ? s2 : s1;
-      if (mn >= P.k_amb && !unk) mm |= bit;
-      else if (s1 >= P.k2) ma |= bit;
-      else if (s2 >= P.k2) mb |= bit;
-    }
-  }
-  E2Eval e;
   const uint64_t ab = ma | mb;                       // "^[^A]*B" -> swap (:537-540)
   e.swapped = (ab && ((mb >> __builtin_ctzll(ab)) & 1ull)) ? 1 : 0;
   e.mm = mm;
   e.mA = e.swapped ? mb : ma;
   e.mB = e.swapped ? ma : mb;
-  int64_t tot = 0, amb = 0;
-  int state = 0;
-  bool dir_ok = true;
-  for (uint64_t r = um; r; r &= r - 1) {             // "^A+B+A+$" without '~' (:542)
-    const int g = __builtin_ctzll(r);
-    const uint64_t bit = 1ull << g;
-    const char c = (mm & bit) ? '*' : (e.mA & bit) ? 'A' : (e.mB & bit) ? 'B' : '!';
-    if (c != '!') {
-      tot += sh.len[g];
-      if (c == '*') amb += sh.len[g];
-    }
-    if (state == 0) { if (c == 'A') state = 1; else dir_ok = false; }
-    else if (state == 1) { if (c == 'B') state = 2; else if (c != 'A') dir_ok = false; }
-    else if (state == 2) { if (c == 'A') state = 3; else if (c != 'B') dir_ok = false; }
-    else { if (c != 'A') dir_ok = false; }
+  // "^A+B+A+$" over the unmasked loci (:542): every one 'A' or 'B', the 'B's one run of
+  // them with an 'A' on either side
+  e.dir = 0;
+  if (e.mB && (e.mA | e.mB) == um) {
+    const int lo = __builtin_ctzll(e.mB), hi = 63 - __builtin_clzll(e.mB);
+    const uint64_t from_lo = ~0ull << lo, to_hi = ~0ull >> (63 - hi);
+    e.dir = ((from_lo & to_hi & um) == e.mB && (e.mA & ~from_lo) && (e.mA & ~to_hi)) ? 1 : 0;
   }
-  e.dir = (dir_ok && state == 3) ? 1 : 0;
   e.ok = 1;
   if ((double)amb / (double)tot > P.amb_frac) e.ok = 0;                       // :693-702
   if (P.clade_genes >= 0 && min(__popcll(e.mA), __popcll(e.mB)) < P.clade_genes) e.ok = 0;   // :704-708
@@ -1102,7 +1071,89 @@ __device__ __forceinline__ E2Eval e2_eval(const KArgs& K, const E2Shared& sh, in
     if (!e.dir) fa = sh.sibp[x] == py ? (sh.s2[y] | (sh.s1[y] & ~sh.hm[x])) : sh.s1[y];
     if ((fb & e.mB) || (fa & e.mA)) e.ok = 0;
   }
+}
+
+// One lane on its own pair: the rows' values are read once for the rank (np_sum_seq's
+// order) and once for the rest.
+__device__ __forceinline__ E2Eval e2_pair(const KArgs& K, const E2Shared& sh, int a, int b, uint64_t um, int Gu) {
+  const DevParams& P = K.p;
+  const bool unk = sh.cl[a] == K.unknown || sh.cl[b] == K.unknown;
+  const int ta = sh.t[a], tb = sh.t[b];
+  const uint64_t pa = sh.pres[a], pb = sh.pres[b];
+  E2Eval e;
+  uint64_t m = um;
+  auto next = [&]() -> double {
+    const int g = __builtin_ctzll(m);
+    m &= m - 1;
+    const double x = e2_at(sh, ta, pa, g), y = e2_at(sh, tb, pb, g);
+    return x < y ? y : x;
+  };
+  e.rank = (0.0 + np_sum_seq(Gu, next)) / (double)Gu;
+  uint64_t mm = 0, ma = 0, mb = 0;
+  int64_t tot = 0, amb = 0;
+  double crit = 0.0;
+  for (uint64_t r = um; r; r &= r - 1) {
+    const int g = __builtin_ctzll(r);
+    const uint64_t bit = 1ull << g;
+    const double s1 = e2_at(sh, ta, pa, g), s2 = e2_at(sh, tb, pb, g);
+    const double mn = s2 < s1 ? s2 : s1, mx = s1 < s2 ? s2 : s1;
+    crit = (r == um || mx < crit) ? mx : crit;
+    if (mn >= P.k_amb && !unk) mm |= bit;
+    else if (s1 >= P.k2) ma |= bit;
+    else if (s2 >= P.k2) mb |= bit;
+    else continue;
+    tot += sh.len[g];
+    if (mm & bit) amb += sh.len[g];
+  }
+  e.crit = crit;
+  e2_checks(K, sh, a, b, um, mm, ma, mb, tot, amb, e);
   return e;
+}
+
+// The whole wave on one pair (a, b wave-uniform, every lane active), lane g on locus g:
+// one LDS round trip for the rows' values; the rank adds the maxima in the
+// same order (np_sum_seq fed from the lanes of um's set bits), the minimum is order-free
+// (values >= +0.0), the synteny masks are ballots.  Every lane returns the same E2Eval.
+__device__ __forceinline__ E2Eval e2_pair_wave(const KArgs& K, const E2Shared& sh, int a, int b, uint64_t um, int Gu) {
+  const DevParams& P = K.p;
+  const int lane = threadIdx.x & 63;
+  const bool in = (um >> lane) & 1ull;
+  const int ln = in ? sh.len[lane] : 0;
+  const bool unk = sh.cl[a] == K.unknown || sh.cl[b] == K.unknown;
+  const double s1 = e2_at(sh, sh.t[a], sh.pres[a], lane), s2 = e2_at(sh, sh.t[b], sh.pres[b], lane);
+  const double mn = s2 < s1 ? s2 : s1, mx = s1 < s2 ? s2 : s1;
+  E2Eval e;
+  uint64_t m = um;
+  auto next = [&]() -> double {
+    const int g = __builtin_ctzll(m);
+    m &= m - 1;
+    return lane_bcast(mx, g);
+  };
+  e.rank = (0.0 + np_sum_seq(Gu, next)) / (double)Gu;
+  const double lo = wave_butterfly(in ? mx : __builtin_inf(), [](double p, double q) { return q < p ? q : p; });
+  e.crit = Gu ? lo : 0.0;
+  const bool star = in && mn >= P.k_amb && !unk;
+  const bool isa = in && !star && s1 >= P.k2;
+  const bool isb = in && !star && !isa && s2 >= P.k2;
+  const uint64_t mm = __ballot(star), ma = __ballot(isa), mb = __ballot(isb);
+  const int64_t tot = wave_sum_dpp((long long)((star || isa || isb) ? ln : 0));
+  const int64_t amb = mm ? wave_sum_dpp((long long)(star ? ln : 0)) : 0;
+  e2_checks(K, sh, a, b, um, mm, ma, mb, tot, amb, e);
+  return e;
+}
+
+// e of lane src (src wave-uniform)
+__device__ __forceinline__ E2Eval e2_bcast(const E2Eval& e, int src) {
+  E2Eval r;
+  r.rank = lane_bcast(e.rank, src);
+  r.crit = lane_bcast(e.crit, src);
+  r.ok = lane_bcast((int)e.ok, src);
+  r.swapped = lane_bcast((int)e.swapped, src);
+  r.dir = lane_bcast((int)e.dir, src);
+  r.mm = lane_bcast(e.mm, src);
+  r.mA = lane_bcast(e.mA, src);
+  r.mB = lane_bcast(e.mB, src);
+  return r;
 }
 
 __device__ __forceinline__ int e2_wave_lca(const KArgs& K, int acc) {
@@ -1233,13 +1284,13 @@ __device__ __forceinline__ bool sp_two(const SArgs& S, E2Shared& sh, int c, int 
   }
   __syncthreads();
   // the potential clades in some candidate pair: the only ones whose parent, listed parent
-  // and sister masks the LGT checks read (e2_eval)
+  // and sister masks the LGT checks read (e2_checks)
   uint64_t memb = 0;
   for (int q = lane; q < nc; q += 64) memb |= (1ull << (sh.cand[q] & 0xFF)) | (1ull << (sh.cand[q] >> 8));
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) memb |= (uint64_t)__shfl_xor((long long)memb, off, 64);
+  memb = wave_or_dpp(memb);
   SLAP(2);
   SSTAT(11, nc);
+  SSTAT(nc == 0 ? 25 : 15 + min(nc, 9), 1);
   if (P.sister_on && memb) {
     const bool me = (memb >> lane) & 1ull;
     const int my_cl = me ? sh.cl[lane] : -1;
@@ -1275,35 +1326,50 @@ __device__ __forceinline__ bool sp_two(const SArgs& S, E2Shared& sh, int c, int 
     __syncthreads();
   }
   SLAP(3);
-  // pass 1: the best candidate pair by (rank, pair index)
+  // pass 1: every candidate pair evaluated once, pair q's E2Eval kept on lane q (q < 64), and
+  // the best pair (bi, bj) by (rank, pair index) with its evaluation.  Few pairs (nearly
+  // every contig has one): the whole wave on each in turn, the best chosen as they come;
+  // more: a lane per pair, the best over the lanes, fetched from the lane that holds it.
   double pr = -__builtin_inf();
-  long long pk = -1;
-  if (nc > 0) {
+  int pk = -1, bi = 0, bj = 0;                       // (pair index i * Pp + j < 64 * 64)
+  E2Eval mine = {}, be = {};
+  if (nc > 0 && nc <= kE2WavePairs) {
+    SSTAT(26, 1);
+    for (int q = 0; q < nc; ++q) {
+      const int i = sh.cand[q] & 0xFF, j = sh.cand[q] >> 8;
+      const E2Eval e = e2_pair_wave(K, sh, i, j, um, Gu);
+      if (lane == q) mine = e;
+      if (better(e.rank, i * Pp + j, pr, pk)) { pr = e.rank; pk = i * Pp + j; bi = i; bj = j; be = e; }
+    }
+  } else if (nc > 0) {
     for (int q = lane; q < nc; q += 64) {
       const int i = sh.cand[q] & 0xFF, j = sh.cand[q] >> 8;
-      const double r = e2_rank(sh, i, j, um, Gu);
-      const long long key = (long long)i * Pp + j;
-      if (better(r, key, pr, pk)) { pr = r; pk = key; }
+      const E2Eval e = e2_pair(K, sh, i, j, um, Gu);
+      if (q < 64) mine = e;
+      if (better(e.rank, i * Pp + j, pr, pk)) { pr = e.rank; pk = i * Pp + j; }
     }
     each_stride([&](auto J) {
       constexpr int js = decltype(J)::value;
       const double r2 = xor_lanes<js>(pr);
-      const long long k2 = xor_lanes<js>(pk);
+      const int k2 = xor_lanes<js>(pk);
       if (better(r2, k2, pr, pk)) { pr = r2; pk = k2; }
     });
+    bi = pk / Pp, bj = pk % Pp;
+    // (past 64 pairs a lane's best may be a later pair than the one it keeps)
+    const bool mine_best = lane < nc && sh.cand[lane] == (bi | (bj << 8));
+    be = nc <= 64 ? e2_bcast(mine, __builtin_ctzll(__ballot(mine_best))) : e2_pair(K, sh, bi, bj, um, Gu);
   }
   SLAP(4);
   if (pk >= 0) {
-    const int bi = (int)(pk / Pp), bj = (int)(pk % Pp);
-    const E2Eval be = e2_eval(K, sh, bi, bj, um);
     // pass 2: options within --range of the best get the LGT checks (:636-639)
     int n_in = 0;
     bool all_ok = true, all_same = true;
     uint64_t b1 = 0, b2 = 0;
     for (int q = lane; q < nc; q += 64) {
       const int i = sh.cand[q] & 0xFF, j = sh.cand[q] >> 8;
-      if ((pr - e2_rank(sh, i, j, um, Gu)) <= P.range) {
-        const E2Eval e = e2_eval(K, sh, i, j, um);
+      E2Eval e = mine;
+      if (q >= 64) e = e2_pair(K, sh, i, j, um, Gu);
+      if ((pr - e.rank) <= P.range) {
         ++n_in;
         all_ok = all_ok && e.ok;
         all_same = all_same && e.mm == be.mm && e.mA == be.mA && e.mB == be.mB;
@@ -1311,12 +1377,9 @@ __device__ __forceinline__ bool sp_two(const SArgs& S, E2Shared& sh, int c, int 
         b2 |= 1ull << (e.swapped ? i : j);
       }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      n_in += __shfl_xor(n_in, off, 64);
-      b1 |= (uint64_t)__shfl_xor((long long)b1, off, 64);
-      b2 |= (uint64_t)__shfl_xor((long long)b2, off, 64);
-    }
+    n_in = wave_sum_dpp(n_in);
+    b1 = wave_or_dpp(b1);
+    b2 = wave_or_dpp(b2);
     all_ok = __ballot(!all_ok) == 0ull;
     all_same = __ballot(!all_same) == 0ull;
     // meld_two (:640-669): 0 none, 1 best as is, 2 meld, 3 unchecked best, 4 upstream crash
@@ -1359,19 +1422,8 @@ __device__ __forceinline__ bool sp_two(const SArgs& S, E2Shared& sh, int c, int 
         K.syn[l0 + lane] = !(um & bit) ? '~' : (be.mm & bit) ? '*' : (be.mA & bit) ? 'A' : (be.mB & bit) ? 'B' : '!';
       }
       if (lane == 0) {
-        double bcrit = 0.0;                          // sp_pair_crit: min over the unmasked loci
-        bool first = true;
-        const int ta = sh.t[bi], tb = sh.t[bj];
-        const uint64_t pa = sh.pres[bi], pb = sh.pres[bj];
-        for (uint64_t r = um; r; r &= r - 1) {
-          const int g = __builtin_ctzll(r);
-          const double x = e2_at(sh, ta, pa, g), y = e2_at(sh, tb, pb, g);
-          const double m = x < y ? y : x;
-          bcrit = (first || m < bcrit) ? m : bcrit;
-          first = false;
-        }
         K.call[c] = WF_CALL_LGT;
-        K.crit[c] = bcrit;
+        K.crit[c] = be.crit;
         K.rank[c] = pr;
         K.dir[c] = (int8_t)be.dir;
         K.c1[c] = kind == 2 ? lca1 : sh.cl[be.swapped ? bj : bi];

@@ -1775,7 +1775,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_decide_big(const SArgs S, int lev
 }
 
 #include "wf_sparse.h"
-WF_STAMP_READER(sparse, g_sstamps, 16)
+WF_STAMP_READER(sparse, g_sstamps, 32)
 WF_STAMP_READER(big, g_bstamps, 48)
 
 int bits_for(int64_t v) {   // bits to hold values 0..v

@@ -7,7 +7,8 @@
 //   WLAP / WSTAT              the first wave form, every 16th contig (g_wstamps;
 //                             -DWF_STAMPS_ROLL=1: the roll-up launches instead of level 0)
 //   TLAP                      the level-0 triage, every 16th contig (g_tstamps)
-//   SLAP / SSTAT              sp_two, every 8th contig (g_sstamps)
+//   SLAP / SSTAT              sp_two, every 8th contig (g_sstamps; 16-24: the histogram of
+//                             candidate pairs, 1..8 and more; 25: none; 26: wave-form calls)
 //   BLAP / BSTAT              sp_level (k_big_sparse, k_dump_sparse<0>), every 8th (g_bstamps)
 #pragma once
 #ifdef WF_STAMPS
@@ -65,7 +66,7 @@ __device__ unsigned long long g_tstamps[16];
     if (tsamp_ && lane == 0) atomicAdd(&g_tstamps[i], n_ - tlap_);                  \
     tlap_ = n_;                                                                     \
   } while (0)
-__device__ unsigned long long g_sstamps[16];
+__device__ unsigned long long g_sstamps[32];
 #define SLAP_MARK(c) unsigned long long slap_ = __builtin_amdgcn_s_memtime(); const bool ssamp_ = ((c) & 7) == 0
 #define SLAP(i)                                                                     \
   do {                                                                              \
