@@ -200,7 +200,8 @@ int main() {
     CHECK(wf_score(ctx, &v, &p, &c.r) == WF_OK);
     for (int i = 0; i < v.n_contigs; ++i)
       CHECK(a.call[i] == c.call[i] && a.crit[i] == c.crit[i] && a.rank[i] == c.rank[i] && a.c1[i] == c.c1[i]);
-    CHECK(wf_set_option(ctx, WF_OPT_SPARSE_BIG, 1) == WF_OK);
+    CHECK(wf_set_option(ctx, WF_OPT_SPARSE_BIG, 1) == WF_E_BADINPUT);   // (retired with ABI 4)
+    CHECK(wf_set_option(ctx, WF_OPT_SPARSE_BIG, 3) == WF_OK);           // the default form again
     CHECK(wf_set_mode(ctx, WF_MODE_LEVEL0) == WF_OK);
   }
 

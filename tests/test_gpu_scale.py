@@ -265,6 +265,55 @@ def test_stress_front_end_matches_five_launch_form(genes, decoys):
     assert_same(slice_results(fused, batch, 0, 3), oracle_results(contigs, sub, tax), sub)
 
 
+def attachments_per_contig(batch):
+    """Hit-locus attachments of each contig by the reference's rule (orgscorer.py:359-368,
+    unstranded): scov >= --min-scov and overlap / shorter interval >= --min-overlap."""
+    out = np.zeros(batch.n_contigs, np.int64)
+    for c in range(batch.n_contigs):
+        h0, h1 = int(batch.hit_off[c]), int(batch.hit_off[c + 1])
+        l0, l1 = int(batch.loc_off[c]), int(batch.loc_off[c + 1])
+        qlo, qhi = batch.hit_qlo[h0:h1, None].astype(np.int64), batch.hit_qhi[h0:h1, None].astype(np.int64)
+        lo = np.minimum(batch.loc_start[l0:l1], batch.loc_end[l0:l1])[None, :].astype(np.int64)
+        hi = np.maximum(batch.loc_start[l0:l1], batch.loc_end[l0:l1])[None, :].astype(np.int64)
+        ov = np.minimum(qhi, hi) - np.maximum(qlo, lo) + 1
+        den = np.minimum(qhi - qlo + 1, hi - lo + 1)
+        ok = (ov > 0) & (ov / den >= PARAMS["min_overlap"]) & (batch.hit_scov[h0:h1, None] >= PARAMS["min_scov"])
+        out[c] = ok.sum()
+    return out
+
+
+def test_device_radix_route_of_a_whole_level():
+    """The third sort route of the staged levels: a contig of more than 8,192 attachments
+    (kRadixMax, what the LDS radix sort holds) makes every level of the call sort with the
+    device radix sort of the whole level and cut its segments from flags over the sorted keys
+    (sort_cap 0) -- the 2,420-attachment contigs beside it included, which alone would take
+    the per-contig bitonic sort.  Default form against the staged form and against the
+    --write-details path, and the oracle's records on a large and a small contig."""
+    assert not PARAMS["stranded"]
+    big = synth.generate(n=2, genes=20, clades=300, decoys=440, lgt_frac=0.5, seed=17, name_prefix="big")
+    small = synth.generate(n=6, genes=20, clades=300, decoys=120, lgt_frac=0.5, seed=17)
+    (b1, tax), (b2, tax2) = synth.to_batch(big), synth.to_batch(small)
+    assert list(tax.names) == list(tax2.names)
+    batch = concat_batches([b2.slice(0, 3), b1, b2.slice(3, 6)])   # contigs 3 and 4 are the large ones
+    att = attachments_per_contig(batch)
+    assert att.max() > 8192 and att.argmax() == 3
+    assert (att <= 4096).any() and att[0] <= 4096
+    s = engine.GpuScorer(0)
+    s.set_taxonomy(tax)
+    fused = s.score(batch, PARAMS)
+    details, _ = s.score_details(batch, PARAMS)
+    s.close()
+    assert not fused.status.any()
+    assert (fused.iterations > 1).any()
+    assert_same(fused, details, batch)
+    assert_same(score(batch, tax, mode="staged"), fused, batch)
+    for at, sub in ((3, b1.slice(0, 1)), (0, b2.slice(0, 1))):     # a large contig, a small one (two levels)
+        contigs = orc.score_contigs(dict(zip(sub.contig_names, sub.contig_lengths.tolist())),
+                                    oracle_loci_from_batch(sub), oracle_hits_from_batch(sub, tax),
+                                    orc.Taxonomy(big.tax.edges), orc.Params(**PARAMS))
+        assert_same(slice_results(fused, batch, at, at + 1), oracle_results(contigs, sub, tax), sub)
+
+
 def test_cfg5_shard_and_embedded_fixture(tmp_path):
     """The cfg5 per-GPU share at 8 GPUs (6,250 stress contigs, ~31 M hits, 5,000 clades):
     equal to its two halves and to the all-segment-table staged form; the reference-generated

@@ -83,8 +83,8 @@ struct SArgs {
   int32_t* big2_list;            // ... of those, the ones k_big_sparse declines (counters[1])
   char* sp_ws;                   // k_big_sparse: HBM scratch, kSpSlot bytes per wave
   int32_t* two_list;             // (rank, contig) pairs that need explain_two (counters[5])
-  int32_t* one_list;             // (rank, contig) pairs for the dense explain_one workgroup
-                                 // (counters[6]); null: every active contig goes there
+  int32_t* one_list;             // (rank, contig) pairs k_one hands to k_decide for the whole level
+                                 // (counters[6]): more than 63 loci and nothing it can take itself
   int32_t* seg_nleaf;            // [segments + 1] numpy leaves per segment
   int32_t* leaf_off;             // [segments + 1] exclusive scan of seg_nleaf
   int32_t* leaf_seg;             // [leaves] segment of each leaf
@@ -104,10 +104,6 @@ struct SArgs {
   int sort_cap;                  // per-contig LDS sort capacity: a power of 2 <= 4,096 (bitonic), a
                                  // multiple of 512 above (the LDS radix sort), 0: device radix sort
   int force_big;                 // WF_OPT_SPARSE_BIG 2: k_one hands every contig over
-  int route_sparse;              // WF_OPT_SPARSE_BIG 2, 3: every k_decide contig to k_big_sparse
-  int sparse_on;                 // WF_OPT_SPARSE_BIG != 0: k_big_sparse runs
-  const unsigned long long* in_counts;   // this level's counts on the device (null: the
-                                         // kernel arguments are exact)
   // Level-0 segment tables the first wave form hands to k_dump_sparse: contigs it leaves at
   // explain_two (or at an unproven --weak-loci assign-unknown row), every mean evaluated
   int64_t dump_cap;              // entries dump_cg / dump_mean hold (0: no hand-over)
@@ -128,7 +124,8 @@ struct SArgs {
   int n_tax;
   int wave_two;                  // WF_OPT_WAVE_TWO: 1 the first form hands explain_two's inputs to
                                  // k_dump_sparse<1> as a compact table, 2 it also settles the
-                                 // ones with no candidate pair itself (0: whole tables only)
+                                 // ones with no candidate pair itself (left 0 where there is no
+                                 // hand-over: dump_cap 0)
   int32_t* roll_next;            // contigs raised at this level (null: no wave levels)
   unsigned long long* roll_next_n;
   unsigned long long* fail_ctr;

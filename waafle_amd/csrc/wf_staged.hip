@@ -8,17 +8,28 @@
 //               k_att_contig<1>                site ranges (:371-382), annotation winners
 //                                              in LDS (:383-392)
 //   per level   k_sort_contig                  per-contig LDS sort of (contig rank, clade,
-//                                              locus) keys (device radix sort for huge
-//                                              contigs) -> segments = equal keys (:394-406)
-//               k_seg_flags + scan + k_segs    segment boundaries
+//                                              locus) keys -> segments = equal keys (:394-406);
+//                                              k_seg_build: segment boundaries
+//               (k_front_radix                 4,097..8,192 attachments: LDS radix sort, segments
+//                                              and means in one launch; k_keys_active + device
+//                                              radix sort + k_seg_flags + scan + k_segs: more)
 //               k_seg_rec                      thread per one-run segment: exact mean
+//               k_seg_wave                     wave per segment of 5..64 attachments
 //               k_leaf + k_seg_combine         lane per numpy leaf, thread per segment: exact
 //                                              mean of the other segments
-//               k_one                          wave per contig: explain_one (+ meld_one)
-//               k_decide / k_decide_big        workgroup per contig: maxes, weak loci,
-//                                              explain_one/two, melds, LGT filters
-//                                              (decide_level, shared with the fused form);
-//                                              raised contigs re-keyed to parents (:431-445)
+//               k_one                          wave per contig: explain_one (+ meld_one); the
+//                                              others handed on by locus count
+//               k_big_sparse (wf_sparse.h)     <= 63 loci, wave per contig: the level decided
+//                                              from the segment table
+//               k_decide / k_decide_big        > 63 loci (LDS arena), and what k_big_sparse
+//                                              declines (HBM slot): the dense gene-score
+//                                              matrix, maxes, weak loci, explain_one/two,
+//                                              melds, LGT filters (decide_level, shared with
+//                                              the fused form)
+//               every decision                 raised contigs re-keyed to parents (:431-445)
+//
+// The host side (staged_run, at the end of this file) runs the wave kernels of wf_triage.hip
+// and wf_fast.hip first and stages only the contigs they hand over.
 //
 // The numpy pairwise-sum leaf tables depend only on the length of a buffer (<= 8192), so
 // they are generated once per context into a device table (k_lut_*), with the same
@@ -54,17 +65,6 @@ __device__ __forceinline__ int lower_bound_i32(const int32_t* a, int n, int x) {
     if (a[mid] < x) lo = mid + 1; else hi = mid;
   }
   return lo;
-}
-
-// Counts of the current level: from the host (kernel arguments) when it knows them, else
-// from the previous level's device counter word (rank slots << 40 | attachments) -- the
-// pipelined levels (staged_score) enqueue a level before the host has read that word.
-__device__ __forceinline__ void lvl_counts(const SArgs& S, int& n_act, int64_t& n_keys) {
-  if (S.in_counts) {
-    const unsigned long long v = *S.in_counts;
-    n_act = (int)(v >> 40);
-    n_keys = (int64_t)(v & ((1ull << 40) - 1));
-  }
 }
 
 __device__ __forceinline__ int seg_count(const SArgs& S, int64_t n_keys) {
@@ -316,8 +316,6 @@ static_assert(kSortMax <= (1 << kSortIdxBits), "contig-local index field");
 template <int NT>
 __global__ __launch_bounds__(NT) void k_sort_contig(const SArgs S, int n_act,
                                                           int level, uint64_t* keys, int32_t* vals) {
-  int64_t n_keys_ = 0;
-  lvl_counts(S, n_act, n_keys_);
   extern __shared__ __attribute__((aligned(16))) char smem[];
   uint64_t* sk = reinterpret_cast<uint64_t*>(smem);
   __shared__ int s_red[NT / 64];
@@ -572,8 +570,6 @@ __device__ __forceinline__ int radix_sort_packed(const SArgs& S, int64_t a0, int
 
 __global__ __launch_bounds__(kRadixNT) void k_sort_radix(const SArgs S, int n_act, int level, uint64_t* keys,
                                                        int32_t* vals) {
-  int64_t n_keys_ = 0;
-  lvl_counts(S, n_act, n_keys_);
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const RadixLds R(smem, S.sort_cap);                  // (the level's largest contig, rounded up)
   __shared__ int s_red[kRadixNT / 64];
@@ -616,7 +612,6 @@ __global__ __launch_bounds__(kRadixNT) void k_sort_radix(const SArgs S, int n_ac
 // attachments gathered into sorted order, the rank -> first segment map and the segment
 // total.  Replaces the flag / scan / segment / gather / rank-map kernels of the radix path.
 __global__ __launch_bounds__(64) void k_seg_build(const SArgs S, int n_act, int level, int64_t n_keys) {
-  lvl_counts(S, n_act, n_keys);
   const int lane = threadIdx.x;
   if (blockIdx.x == 0 && lane == 0 && n_keys > 0) {
     const int total = S.crank_first[n_act];
@@ -674,7 +669,6 @@ __global__ __launch_bounds__(64) void k_seg_build(const SArgs S, int n_act, int 
 // per step (segment heads counted per wave by ballot, then across the waves through LDS)
 // instead of one wave stepping 64 keys at a time through ~5,000.
 __global__ __launch_bounds__(kRadixNT) void k_seg_build_wide(const SArgs S, int n_act, int level, int64_t n_keys) {
-  lvl_counts(S, n_act, n_keys);
   constexpr int kW = kRadixNT / 64;
   __shared__ int s_glen[64];
   __shared__ int s_cnt[kW];
@@ -761,15 +755,11 @@ __global__ __launch_bounds__(kRadixNT) void k_seg_build_wide(const SArgs S, int 
 }
 
 __global__ void k_seg_flags(const SArgs S, int64_t n) {
-  int n_act_ = 0;
-  lvl_counts(S, n_act_, n);
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) S.flags[i] = (i == 0 || S.keys[i] != S.keys[i - 1]) ? 1 : 0;
 }
 
 __global__ void k_segs(const SArgs S, int64_t n) {
-  int n_act_ = 0;
-  lvl_counts(S, n_act_, n);
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   if (S.flags[i]) {
@@ -783,7 +773,6 @@ __global__ void k_segs(const SArgs S, int64_t n) {
 // crank_first[cr] = first segment of active contig cr (segments are sorted by rank; ranks
 // without segments get the next rank's start), crank_first[n_act] = segment count.
 __global__ void k_crank_first(const SArgs S, int64_t n_keys, int n_act) {
-  lvl_counts(S, n_act, n_keys);
   const int ns = seg_count(S, n_keys);
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s > ns) return;
@@ -794,8 +783,6 @@ __global__ void k_crank_first(const SArgs S, int64_t n_keys, int n_act) {
 
 // Attachments copied into sorted order, so each segment's are contiguous.
 __global__ void k_gather(const SArgs S, int64_t n) {
-  int n_act_ = 0;
-  lvl_counts(S, n_act_, n);
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int a = S.vals[i];
@@ -967,8 +954,6 @@ __device__ __forceinline__ void wave_list_add(const SArgs& S, int64_t s, bool to
 }
 
 __global__ void k_seg_rec(const SArgs S, int64_t n_keys) {
-  int n_act_ = 0;
-  lvl_counts(S, n_act_, n_keys);
   const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (s > n_keys) return;
   int nl = 0;
@@ -1203,8 +1188,6 @@ __device__ __forceinline__ int2 leaf_span(const SArgs& S, int len, int j) {
 }
 
 __global__ void k_leaf_expand(const SArgs S, int64_t n_keys) {
-  int n_act_ = 0;
-  lvl_counts(S, n_act_, n_keys);
   const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= seg_count(S, n_keys)) return;
   const int o = S.leaf_off[s], n = S.seg_nleaf[s];
@@ -1217,8 +1200,6 @@ __global__ void k_leaf_expand(const SArgs S, int64_t n_keys) {
 // combined as ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) with xor shuffles (float addition is
 // commutative, so the result is exact).  Wave-uniform loop: every lane runs the same trips.
 __global__ void k_leaf(const SArgs S, int64_t n_keys) {
-  int n_act_ = 0;
-  lvl_counts(S, n_act_, n_keys);
   const int ns = seg_count(S, n_keys);
   const int TL = S.leaf_off[ns];
   const SortedSrc src{S.satt_lohi, S.satt_sc};
@@ -1290,8 +1271,6 @@ __device__ __forceinline__ void seg_combine_one(const SArgs& S, int s) {
 // first leaf): a grid-stride loop over the level's leaves instead of a thread for every
 // segment of the level (most of which k_seg_rec already finished).
 __global__ void k_seg_combine(const SArgs S, int64_t n_keys) {
-  int n_act_ = 0;
-  lvl_counts(S, n_act_, n_keys);
   const int TL = S.leaf_off[seg_count(S, n_keys)];
   for (int jl = blockIdx.x * blockDim.x + threadIdx.x; jl < TL; jl += gridDim.x * blockDim.x) {
     const int s = S.leaf_seg[jl];
@@ -1307,9 +1286,12 @@ __global__ void k_seg_combine(const SArgs S, int64_t n_keys) {
 // itself (crit = min, rank = numpy-order mean over the unmasked loci, zeros where the clade
 // has no segment).  The best option is a wave argmax by (rank, larger clade id) -- the
 // sorted-order tie policy of decide_one -- and the winner's synteny is 'A' on every unmasked
-// locus ('~' elsewhere), since its crit >= k1.  Contigs with more segments than the stage
-// holds, more than 64 loci or --weak-loci assign-unknown (virtual "Unknown" row) go to the
-// dense workgroup (k_decide<1>); contigs without a one-clade option go to explain_two.
+// locus ('~' elsewhere), since its crit >= k1.  Contigs it cannot take -- more segments than
+// the stage holds, more than 64 loci, --weak-loci assign-unknown (virtual "Unknown" row) --
+// and contigs without a one-clade option (explain_two) are handed on: at most 63 loci to the
+// segment-table decision (big_list: k_big_sparse), more to the dense workgroup (one_list the
+// whole level, two_list explain_two: k_decide).
+//
 // Upper bound of decide_contig's arena for P clade rows (segments + 1) and G loci: every
 // take() of decide_contig with its 16-byte alignment, plus the mask-class workspace.
 __host__ __device__ int64_t arena_bound(int64_t P, int64_t G) {
@@ -1329,7 +1311,6 @@ constexpr int kOneCap = 384;
 // held across the loop it spilled 64 SGPRs)
 __global__ __launch_bounds__(64) void k_one(const SArgs S_arg, int n_act, int level,
                                             int64_t n_keys) {
-  lvl_counts(S_arg, n_act, n_keys);
   __shared__ int2 s_cg[kOneCap];
   __shared__ double s_v[kOneCap];
   __shared__ double s_rank[kOneCap];     // rank of the option whose clade run starts here, or -1
@@ -1338,13 +1319,11 @@ __global__ __launch_bounds__(64) void k_one(const SArgs S_arg, int n_act, int le
   __shared__ unsigned long long s_head[kOneCap / 64];   // clade-run heads, one ballot per 64
   __shared__ int s_cnt;
   const int lane = threadIdx.x;
-  // straight to the segment-table decision (k_big_sparse): the dense matrix cannot fit the
-  // arena (or every decision is routed there; routed ones with few segments take explain_one
-  // here first)
+  // straight to the segment-table decision (k_big_sparse): every contig of at most 63 loci
+  // that explain_one cannot take here (more segments than the stage holds, --weak-loci
+  // assign-unknown), or all of them (WF_OPT_SPARSE_BIG 2)
   auto straight_big = [](const SArgs& S, int G, int ns) {
-    return S.sparse_on && G <= 63 &&
-           (S.route_sparse || (ns > kOneCap && arena_bound(ns + 1, G) + 4096 > S.dec_lds_bytes)) &&
-           !(S.route_sparse && !S.force_big && ns <= kOneCap && S.k.p.weak != 2);
+    return G <= 63 && (S.force_big || ns > kOneCap || S.k.p.weak == 2);
   };
   // those first, a contig per lane: one list append (and one need_bytes max) per wave instead
   // of one contended atomic per contig (the cfg5 stress levels: every contig goes there)
@@ -1393,8 +1372,8 @@ __global__ __launch_bounds__(64) void k_one(const SArgs S_arg, int n_act, int le
     const int so = n_keys > 0 ? S.crank_first[cr] : 0;
     const int ns = (n_keys > 0 ? S.crank_first[cr + 1] : 0) - so;
     if (straight_big(S, G, ns)) continue;               // (listed above)
-    const bool to_sparse = S.sparse_on && G <= 63;
-    // routed decisions without an explain_one option go to k_big_sparse for explain_two
+    const bool to_sparse = G <= 63;
+    // contigs without an explain_one option go to k_big_sparse for explain_two
     auto push_big = [&]() {
       if (lane == 0) {
         const int64_t need = arena_bound(ns + 1, G) + 4096;
@@ -1490,7 +1469,7 @@ __global__ __launch_bounds__(64) void k_one(const SArgs S_arg, int n_act, int le
       if (better(r2, k2, br, bk)) { br = r2; bk = k2; bcrit = c2; }
     }
     if (bk < 0) {                                          // explain_two (:570)
-      if (to_sparse && S.route_sparse) {
+      if (to_sparse) {
         push_big();
         continue;
       }
@@ -1544,8 +1523,8 @@ __global__ __launch_bounds__(64) void k_one(const SArgs S_arg, int n_act, int le
 // level (rows = clades in id order, the virtual "Unknown" row of --weak-loci
 // assign-unknown included) from the contig's segments, then runs decide_level.
 // Returns false when the arena is too small (caller hands the contig to the HBM tier).
-// PHASE 0: the whole level (HBM-slot tier); 1: prologue + explain_one, contigs without a
-// one-clade explanation are queued for phase 2; 2: prologue + explain_two + roll-up.
+// PHASE 0: the whole level; 2: prologue + explain_two + roll-up (k_one found no one-clade
+// explanation).
 template <int NT, int PHASE>
 __device__ __forceinline__ bool decide_contig(const SArgs& S, int c, int cr, int level, char* abase, int64_t acap,
                               Ctl& ctl, int64_t n_keys, bool in_lds = true) {
@@ -1593,9 +1572,9 @@ __device__ __forceinline__ bool decide_contig(const SArgs& S, int c, int cr, int
     C.xcap = cls_bytes(Pmax);
     C.xws = ar.take<char>(C.xcap);
   }
-  // routed decisions go to k_big_sparse -- unless it would decline them (> 63 loci: the
-  // segment-table form's locus masks), then the arena decides here
-  if (!ar.fits() || (in_lds && S.route_sparse && G <= 63)) {
+  // in the LDS arena (k_decide) only > 63 loci are decided: the others go to k_big_sparse
+  // (its locus masks hold 63), which hands back here, in an HBM slot, what it declines
+  if (!ar.fits() || (in_lds && G <= 63)) {
     if (tid == 0) K.need[c] = ar.used + 4096;
     __syncthreads();
     return false;
@@ -1650,23 +1629,12 @@ __device__ __forceinline__ bool decide_contig(const SArgs& S, int c, int cr, int
   bool first = level == 0;
   int64_t pair_evals = level == 0 ? 0 : K.pair_evals[c];
   int dec;
+  static_assert(PHASE == 0 || PHASE == 2, "decide_contig: the whole level or explain_two");
   if (PHASE == 0) {
     dec = decide_level<NT>(K, C, ctl, c, Pn, iteration, first, pair_evals);
   } else {
     dec = decide_prologue<NT>(K, C, ctl, Pn, first);
-    if (PHASE == 1 && dec == kDecNext) {
-      dec = decide_one<NT>(K, C, ctl, c, Pn, iteration, pair_evals);
-      if (dec == kDecNext) {
-        if (tid == 0) {
-          const int slot = (int)atomicAdd(&S.counters[5], 1ull);
-          S.two_list[2 * slot] = cr;
-          S.two_list[2 * slot + 1] = c;
-        }
-        return true;
-      }
-    } else if (PHASE == 2 && dec == kDecNext) {
-      dec = decide_two<NT>(K, C, ctl, c, Pn, iteration, pair_evals);
-    }
+    if (dec == kDecNext) dec = decide_two<NT>(K, C, ctl, c, Pn, iteration, pair_evals);
   }
   if (dec == kDecDone) return true;
   if (dec == kDecRaise && iteration + 1 <= kMaxIter) {
@@ -1713,38 +1681,21 @@ __device__ __forceinline__ bool decide_contig(const SArgs& S, int c, int cr, int
 
 constexpr int kDecNT = 64;   // one wave per contig decision: no cross-wave barriers
 
-template <int PHASE, int NT = kDecNT>
-__global__ __launch_bounds__(NT, 2) void k_decide(const SArgs S, int n_act,
-                                                   int level, int64_t n_keys) {
-  lvl_counts(S, n_act, n_keys);
+// The dense decision in the LDS arena, one launch for both of k_one's lists: the contigs it
+// handed over (one_list, counters[6]) get the whole level, the contigs it left open (two_list,
+// counters[5]) explain_two.  What the arena cannot hold, or k_big_sparse should decide, goes
+// to big_list.
+__global__ __launch_bounds__(kDecNT, 2) void k_decide(const SArgs S, int level, int64_t n_keys) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ Ctl ctl;
-  if constexpr (PHASE == 3) {
-    // one launch for both lists: the contigs k_one handed over get the whole level
-    // (PHASE 0 logic), the contigs it left open get explain_two (PHASE 2)
-    const int c1 = (int)S.counters[6], c2 = (int)S.counters[5];
-    for (int i = blockIdx.x; i < c1 + c2; i += gridDim.x) {
-      const bool whole = i < c1;
-      const int32_t* L = whole ? S.one_list : S.two_list;
-      const int j = whole ? i : i - c1;
-      const int cr = L[2 * j], c = L[2 * j + 1];
-      const bool ok = whole ? decide_contig<NT, 0>(S, c, cr, level, smem, S.dec_lds_bytes, ctl, n_keys)
-                            : decide_contig<NT, 2>(S, c, cr, level, smem, S.dec_lds_bytes, ctl, n_keys);
-      if (!ok && threadIdx.x == 0) {
-        const int slot = (int)atomicAdd(&S.counters[2], 1ull);
-        S.big_list[2 * slot] = cr;
-        S.big_list[2 * slot + 1] = c;
-        atomicMax(&S.counters[3], (unsigned long long)S.k.need[c]);
-      }
-      __syncthreads();
-    }
-  } else {
-  const int32_t* list = PHASE == 1 ? S.one_list : S.two_list;
-  const int count = PHASE == 1 ? (list ? (int)S.counters[6] : n_act) : (int)S.counters[5];
-  for (int i = blockIdx.x; i < count; i += gridDim.x) {
-    const int cr = list ? list[2 * i] : i;
-    const int c = list ? list[2 * i + 1] : (S.act ? S.act[cr] : cr);
-    const bool ok = decide_contig<NT, PHASE>(S, c, cr, level, smem, S.dec_lds_bytes, ctl, n_keys);
+  const int c1 = (int)S.counters[6], c2 = (int)S.counters[5];
+  for (int i = blockIdx.x; i < c1 + c2; i += gridDim.x) {
+    const bool whole = i < c1;
+    const int32_t* L = whole ? S.one_list : S.two_list;
+    const int j = whole ? i : i - c1;
+    const int cr = L[2 * j], c = L[2 * j + 1];
+    const bool ok = whole ? decide_contig<kDecNT, 0>(S, c, cr, level, smem, S.dec_lds_bytes, ctl, n_keys)
+                          : decide_contig<kDecNT, 2>(S, c, cr, level, smem, S.dec_lds_bytes, ctl, n_keys);
     if (!ok && threadIdx.x == 0) {
       const int slot = (int)atomicAdd(&S.counters[2], 1ull);
       S.big_list[2 * slot] = cr;
@@ -1753,21 +1704,16 @@ __global__ __launch_bounds__(NT, 2) void k_decide(const SArgs S, int n_act,
     }
     __syncthreads();
   }
-  }
 }
 
-// The dense decision in an HBM slot: the contigs k_big_sparse declined (big2_list,
-// counters[1]), or every contig of big_list (counters[2]) when the sparse form is off.
-__global__ __launch_bounds__(kBlock, 2) void k_decide_big(const SArgs S, int level,
-                                                          int64_t n_keys, int use2) {
-  int n_act_ = 0;
-  lvl_counts(S, n_act_, n_keys);
-  const int count = (int)S.counters[use2 ? 1 : 2];
-  const int32_t* list = use2 ? S.big2_list : S.big_list;
+// The dense decision in an HBM slot, for the contigs k_big_sparse declined (big2_list,
+// counters[1]).
+__global__ __launch_bounds__(kBlock, 2) void k_decide_big(const SArgs S, int level, int64_t n_keys) {
+  const int count = (int)S.counters[1];
   __shared__ Ctl ctl;
   char* base = S.k.big_ws + (int64_t)blockIdx.x * S.k.slot_bytes;
   for (int i = blockIdx.x; i < count; i += gridDim.x) {
-    const int cr = list[2 * i], c = list[2 * i + 1];
+    const int cr = S.big2_list[2 * i], c = S.big2_list[2 * i + 1];
     const bool ok = decide_contig<kBlock, 0>(S, c, cr, level, base, S.k.slot_bytes, ctl, n_keys, false);
     if (!ok && threadIdx.x == 0) S.k.status[c] = WF_E_NOMEM;
     __syncthreads();
@@ -1812,12 +1758,6 @@ struct Buf {
 }  // namespace
 
 
-// The roll-up launches of the first wave form and its level-0 launch over the triage's list
-// take their contigs from a work-queue counter (a static XCD order left a few waves finishing
-// last: roll-up 4.98 -> 4.35, list 2.36 -> 2.00 ms, r5j / r5k).  Levels whose largest contig
-// has 4,097..8,192 attachments sort per contig in LDS (k_sort_radix), not with the device
-// radix sort of the whole level.
-
 struct StagedState {
   int device = 0;
   int cus = 256;
@@ -1830,7 +1770,8 @@ struct StagedState {
   Buf span_cnt, spans;                              // --write-details only
   unsigned long long* host_lvl = nullptr;         // pinned: count word of each level
   hipEvent_t lvl_ev[2] = {nullptr, nullptr};
-  int sparse_big = 3;                // WF_OPT_SPARSE_BIG (2 all, 3 the open decisions; 0/1 retired)
+  int sparse_big = 3;                // WF_OPT_SPARSE_BIG: 2 k_one hands every contig to k_big_sparse, 3 the
+                                     // ones it cannot finish (wf_set_option refuses the retired 0 and 1)
   int sparse_res = -1;               // resident k_big_sparse waves per CU
   int two_res = -1;                  // resident k_dump_sparse<1> (compact tables) waves per CU
   int64_t att_limit = (int64_t(1) << 31) - 1;   // attachments per call (WF_OPT_ATT_LIMIT)
@@ -1991,10 +1932,6 @@ static inline unsigned grid_for(int64_t n, int block = 256) {
   return (unsigned)std::max<int64_t>(1, (n + block - 1) / block);
 }
 
-// Runs the whole path for one batch on stream `s` (synchronising on it between levels).
-// `k` carries device pointers for batch, taxonomy, params and results.
-// Host waits inside a pass: an event polled in a loop wakes the host within microseconds,
-// where a blocking stream synchronisation took tens of microseconds per level.
 // Exclusive scan of n ints by one workgroup (per-contig segment counts -> first segment):
 // one launch with no host-side temp-storage query, where the device scan costs two
 // launches and a host call that is slower than the scan itself.  Thread t owns a
@@ -2055,12 +1992,24 @@ static hipError_t publish_sync(StagedState* st, hipStream_t s, const void* a, in
   return hipSuccess;
 }
 
+// Host waits inside a pass: an event polled in a loop wakes the host within microseconds,
+// where a blocking stream synchronisation took tens of microseconds per level.
 static hipError_t spin_sync(hipStream_t s, hipEvent_t ev) {
   hipError_t e = hipEventRecord(ev, s);
   if (e != hipSuccess) return e;
   while ((e = hipEventQuery(ev)) == hipErrorNotReady) {
   }
   return e;
+}
+
+// Device count words to the host, now: a[0, na) then b[0, nb) into out -- through the mailbox
+// when the context has one, else by copies and a polled event.
+static hipError_t read_counts(StagedState* st, hipStream_t s, const void* a, int na, const void* b, int nb,
+                              unsigned long long* out) {
+  if (st->mbox) return publish_sync(st, s, a, na, b, nb, out);
+  hipError_t e = hipMemcpyAsync(out, a, (size_t)na * 8, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess && nb > 0) e = hipMemcpyAsync(out + na, b, (size_t)nb * 8, hipMemcpyDeviceToHost, s);
+  return e == hipSuccess ? spin_sync(s, st->lvl_ev[0]) : e;
 }
 
 // --write-details: this level's evaluated contigs and segment records (gene scores =
@@ -2177,30 +2126,598 @@ static int two_waves(StagedState* st) {
   return st->two_res;
 }
 
-template <class It>
-static hipError_t scan_list(StagedState* st, hipStream_t s, It in, int64_t* out, int n) {
+// The hipcub two-step: prim(temp storage, its size) with a null pointer only reports the size;
+// then the primitive runs in st->tmp.  (size_buffers sizes tmp for every primitive of the
+// levels before the first of them is enqueued: ensure() drains the stream when it grows.)
+template <class Prim>
+static hipError_t with_tmp(StagedState* st, hipStream_t s, Prim prim) {
   size_t ts = 0;
-  hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, ts, in, out, n, s);
-  if (e != hipSuccess) return e;
-  e = st->tmp.ensure(s, ts);
+  hipError_t e = prim(nullptr, ts);
+  if (e == hipSuccess) e = st->tmp.ensure(s, ts);
   if (e != hipSuccess) return e;
   ts = st->tmp.n;
-  return hipcub::DeviceScan::ExclusiveSum(st->tmp.p, ts, in, out, n, s);
+  return prim(st->tmp.p, ts);
 }
 
+template <class In, class Out>
+static hipError_t scan_list(StagedState* st, hipStream_t s, In in, Out out, int n) {
+  return with_tmp(st, s, [&](void* t, size_t& ts) { return hipcub::DeviceScan::ExclusiveSum(t, ts, in, out, n, s); });
+}
+
+// the indices i < n with flags[i] set, in order, and their count
 template <class Flags>
 static hipError_t select_list(StagedState* st, hipStream_t s, Flags flags, int32_t* out, int64_t* count, int n) {
-  size_t ts = 0;
-  hipError_t e = hipcub::DeviceSelect::Flagged(nullptr, ts, hipcub::CountingInputIterator<int32_t>(0), flags, out,
-                                               count, n, s);
-  if (e != hipSuccess) return e;
-  e = st->tmp.ensure(s, ts);
-  if (e != hipSuccess) return e;
-  ts = st->tmp.n;
-  return hipcub::DeviceSelect::Flagged(st->tmp.p, ts, hipcub::CountingInputIterator<int32_t>(0), flags, out,
-                                       count, n, s);
+  return with_tmp(st, s, [&](void* t, size_t& ts) {
+    return hipcub::DeviceSelect::Flagged(t, ts, hipcub::CountingInputIterator<int32_t>(0), flags, out, count, n, s);
+  });
 }
 
+// ensure() for `count` elements and the typed pointer, so a buffer is named once
+template <class T>
+static hipError_t take(Buf& b, hipStream_t s, size_t count, T*& p) {
+  const hipError_t e = b.ensure(s, count * sizeof(T));
+  p = b.as<T>();
+  return e;
+}
+
+// One staged_run call: what its phases share.
+struct Call {
+  StagedState* st;
+  hipStream_t s;
+  std::string* err;
+  DetailsSink* det;
+  int N, n_tax, max_loci, max_hits;
+  int64_t NH, NL;
+  SArgs sa;                       // the staged kernels' arguments, wired as the phases go
+  bool level0;                    // the wave kernels run first (wave_front)
+  unsigned agrid;                 // k_att_contig's grid: waves per CU
+  // read back by count_lists
+  int64_t A, TLB, max_att;        // attachments, leaf bound, the largest contig's attachments
+  int n_first;                    // contigs whose attachments are built (all, or the hand-over)
+  int n_l0, n_seed;               // contigs of staged level 0, seeds of level 1
+  int64_t keys_l0, keys_seed;     // ... and their attachments
+};
+#define CALL_LOCALS(C)            \
+  StagedState* const st = (C).st; \
+  const hipStream_t s = (C).s;    \
+  std::string* const err = (C).err
+
+// The wave levels (phase 1): levels 1, 2, ... of the first wave form, one launch per level
+// over the contigs the level before raised (work-queue order), each followed by k_dump_sparse
+// on what it hands over.  Enqueued kLevelChunk at a time (a level with an empty list costs two
+// near-empty launches), then the next level's count is read back.  *done: no contig left
+// the wave forms.
+static int wave_levels(Call& C, const SArgs& da, unsigned long long* rcnt, int grid, int grid2, bool* done) {
+  CALL_LOCALS(C);
+  constexpr int kLevelChunk = 5;
+  int64_t* const cnt = st->cnt.as<int64_t>();
+  int64_t* const cleaves = st->cnt_leaves.as<int64_t>();
+  unsigned long long* dctr = st->dump_ctr.as<unsigned long long>();
+  int32_t* roll[2] = {st->roll0.as<int32_t>(), st->roll1.as<int32_t>()};
+  unsigned long long* hcnt = st->host_counters;
+  for (int L = 1;;) {
+    const int L_end = std::min(L + kLevelChunk - 1, kMaxIter);
+    for (; L <= L_end; ++L) {
+      SArgs la = da;
+      la.dump_ctr = dctr + (L & 1);
+      la.dump_ctr_next = dctr + ((L + 1) & 1);
+      la.roll_next = roll[(L + 1) & 1];
+      la.roll_next_n = rcnt + L + 1;
+      la.wq = st->wq.as<unsigned long long>() + L;
+      ST_TRY(launch_level(la, cnt, cleaves, st->pend.as<int32_t>(), roll[L & 1],
+                          reinterpret_cast<const int64_t*>(rcnt + L), L, C.max_hits, st->cus, s));
+      la.wq = nullptr;                             // (a queue for sp_two: r5t, 0.35 ms slower)
+      hipLaunchKernelGGL(k_dump_sparse<1>, dim3(grid2), dim3(64), 0, s, la, cnt, cleaves, L);
+      hipLaunchKernelGGL(k_dump_sparse<0>, dim3(grid), dim3(64), 0, s, la, cnt, cleaves, L);
+      ST_TRY(hipGetLastError());
+    }
+    ST_TRY(read_counts(st, s, rcnt + L, 1, rcnt + kMaxIter + 2, 1, hcnt));
+    if (hcnt[0] == 0 || L > kMaxIter) break;
+  }
+  *done = hcnt[1] == 0;
+  return 0;
+}
+
+// Phase 1, the wave front (wf_triage.hip, wf_fast.hip, wf_sparse.h): the level-0 triage, the
+// first wave form over the contigs it leaves, k_dump_sparse on the segment tables that form
+// hands over, the wave levels, and the second wave form over the other contigs handed over.
+// *done: every contig finished here.  Without the wave kernels (C.level0 off) only the
+// attachments are counted (k_att_contig<0>).
+static int wave_front(Call& C, bool* done) {
+  CALL_LOCALS(C);
+  SArgs& sa = C.sa;
+  const int N = C.N, max_hits = C.max_hits;
+  int64_t* const cnt = st->cnt.as<int64_t>();
+  int64_t* const cleaves = st->cnt_leaves.as<int64_t>();
+  int t_waves = C.level0 ? t_mark(st, s) : -1;          // (the waves span: the wave launches alone)
+  if (C.level0) {
+    int32_t* pend = nullptr;
+    ST_TRY(take(st->pend, s, N, pend));
+    ST_TRY(st->act0.ensure(s, (size_t)N * 4));
+    // The first form hands the contigs it leaves at explain_two (or at an unproven
+    // assign-unknown row) over with their level-0 segment tables, every mean evaluated:
+    // k_dump_sparse decides them from the table (pend 3 -> 0, 2 or 1).  With the hand-over
+    // come the wave levels: the first form also carries the roll-up levels.  (Not when the
+    // second form carries them: st->rollup.)
+    const bool handover = !st->rollup;
+    SArgs da = sa;
+    unsigned long long* rcnt = nullptr;              // [kMaxIter + 2] per-level list counts, fail count
+    if (handover) {
+      int64_t cap = std::min<int64_t>(std::max<int64_t>((int64_t)N * 32, 1 << 16), (1ll << 31) - 4096);
+      if (st->dump_cap > 0) cap = st->dump_cap;      // WF_OPT_DUMP_CAP (tests: the overflow branch)
+      da.dump_cap = cap;
+      ST_TRY(take(st->dump_cg, s, cap, da.dump_cg));
+      ST_TRY(take(st->dump_mean, s, cap, da.dump_mean));
+      ST_TRY(take(st->dump_first, s, (size_t)N + 1, da.dump_first));
+      ST_TRY(take(st->dump_list, s, (size_t)N * 2, da.dump_list));
+      ST_TRY(take(st->dump_ctr, s, 2, da.dump_ctr));
+      ST_TRY(hipMemsetAsync(st->dump_ctr.p, 0, 16, s));
+      ST_TRY(take(st->dump_um, s, N, da.dump_um));
+      ST_TRY(st->roll0.ensure(s, (size_t)N * 4));
+      ST_TRY(take(st->roll1, s, N, da.roll_next));   // level L appends to roll[(L + 1) & 1]
+      ST_TRY(take(st->roll_cnt, s, kMaxIter + 3, rcnt));
+      ST_TRY(st->anc.ensure(s, (size_t)std::max(C.n_tax, 1) * 4));
+      ST_TRY(hipMemsetAsync(st->roll_cnt.p, 0, (kMaxIter + 3) * sizeof(unsigned long long), s));
+      da.n_tax = C.n_tax;
+      da.wave_two = st->wave_two;
+      da.roll_next_n = rcnt + 1;
+      da.fail_ctr = rcnt + kMaxIter + 2;
+    }
+    if (handover || st->triage) {
+      // work queues: [0] the level-0 list, [L] level L's launch.  The roll-up launches and
+      // the level-0 launch over the triage's list take their contigs from a counter (a static
+      // XCD order left a few waves finishing last: roll-up 4.98 -> 4.35, list 2.36 -> 2.00
+      // ms, r5j / r5k)
+      ST_TRY(st->wq.ensure(s, (kMaxIter + 2) * sizeof(unsigned long long)));
+      ST_TRY(hipMemsetAsync(st->wq.p, 0, (kMaxIter + 2) * sizeof(unsigned long long), s));
+    }
+    if (st->triage) {
+      // the triage (wf_triage.hip) decides the contigs explain_one settles from their full
+      // clades; the first wave form runs the rest from its list (count on the device)
+      ST_TRY(st->tri_list.ensure(s, (size_t)N * 4));
+      ST_TRY(st->tri_cnt.ensure(s, 8));
+      if (!da.k.hkey) {                                  // no wf_batch.hit_key: packed here
+        ST_TRY(st->hkey.ensure(s, (size_t)std::max<int64_t>(C.NH, 1) * 4));
+        ST_TRY(pack_keys(da.k, C.NH, st->hkey.as<uint32_t>(), st->cus, s));
+        da.k.hkey = st->hkey.as<uint32_t>();
+        sa.k.hkey = da.k.hkey;                         // (k_att_contig reads it too)
+      }
+      const int t_tri0 = t_mark(st, s);                 // (the triage span: its launch alone)
+      ST_TRY(launch_triage(da, cnt, cleaves, pend, max_hits, st->cus, s));
+      const int t_tri = t_mark(st, s);
+      t_span(st, WF_PHASE_WAVES, t_waves, t_tri0);
+      t_span(st, WF_PHASE_TRIAGE, t_tri0, t_tri);
+      t_waves = t_tri;
+      using PendItT = hipcub::TransformInputIterator<bool, PendIs, const int32_t*>;
+      ST_TRY(select_list(st, s, PendItT(pend, PendIs{kPendTriage}), st->tri_list.as<int32_t>(),
+                         st->tri_cnt.as<int64_t>(), N));
+      SArgs ta = da;                                   // (the list's contigs vary in cost as the roll-up lists')
+      ta.wq = st->wq.as<unsigned long long>();
+      ST_TRY(launch_fast_list(ta, cnt, cleaves, pend, st->tri_list.as<int32_t>(), st->tri_cnt.as<int64_t>(),
+                              max_hits, st->cus, s));
+    } else {
+      ST_TRY(launch_fast(da, cnt, cleaves, pend, max_hits, st->cus, s));
+    }
+    if (handover) {
+      const int t_h0 = t_mark(st, s);
+      t_span(st, WF_PHASE_WAVES, t_waves, t_h0);
+      const int grid = st->cus * sparse_waves(st);
+      ST_TRY(take(st->sp_ws, s, (size_t)grid * kSpSlot, da.sp_ws));
+      da.seg_cg = da.dump_cg; da.seg_mean = da.dump_mean; da.crank_first = da.dump_first;
+      da.seed_pend = pend;
+      da.anc = st->anc.as<int32_t>();                 // (k_dump_sparse: ancestors of level 1)
+      da.dump_ctr_next = da.dump_ctr + 1;
+      const int grid2 = st->cus * two_waves(st);
+      // compact tables (and the level set-up), then whole tables
+      hipLaunchKernelGGL(k_dump_sparse<1>, dim3(grid2), dim3(64), 0, s, da, cnt, cleaves, 0);
+      hipLaunchKernelGGL(k_dump_sparse<0>, dim3(grid), dim3(64), 0, s, da, cnt, cleaves, 0);
+      ST_TRY(hipGetLastError());
+      const int t_h1 = t_mark(st, s);
+      t_span(st, WF_PHASE_HANDOVER, t_h0, t_h1);
+      const int rc = wave_levels(C, da, rcnt, grid, grid2, done);
+      if (rc) return rc;
+      const int t_r1 = t_mark(st, s);
+      t_span(st, WF_PHASE_ROLLUP, t_h1, t_r1);
+      t_waves = t_r1;                                  // the waves span resumes here
+      if (*done) return 0;
+    }
+    // the other contigs it handed over (pend 1) through the second wave form, its list and
+    // count built on the device
+    // (only those whose attachments fit the second form's slice: the others would load every
+    // hit only to be handed on again)
+    using FitIt = hipcub::TransformInputIterator<bool, PendFits, hipcub::CountingInputIterator<int>>;
+    int64_t* const n_fit = st->red.as<int64_t>() + 3;
+    ST_TRY(select_list(st, s, FitIt(hipcub::CountingInputIterator<int>(0),
+                                    PendFits{pend, cnt, max_hits <= 256 ? 256 : 512}),
+                       st->act0.as<int32_t>(), n_fit, N));
+    ST_TRY(launch_full(sa, cnt, cleaves, pend, st->act0.as<int32_t>(), n_fit, max_hits, st->cus, st->rollup, s));
+  } else {
+    hipLaunchKernelGGL((k_att_contig<0, kAttNT>), dim3(C.agrid), dim3(kAttNT), 0, s, sa, cnt, cleaves,
+                       reinterpret_cast<unsigned long long*>(st->red.as<int64_t>() + 1), nullptr, N);
+  }
+  ST_TRY(hipGetLastError());
+  t_span(st, WF_PHASE_WAVES, t_waves, t_mark(st, s));
+  return 0;
+}
+
+// Phase 2, counts and lists: attachment offsets (the scan of the per-contig counts), the leaf
+// bound and the largest contig; after the wave kernels also the contigs they handed over, in
+// contig order (their attachments are built), the staged level-0 list (pend 1) and the
+// level-1 seeds (pend 2), each with compact key bases.  The totals are read back into C.
+static int count_lists(Call& C) {
+  CALL_LOCALS(C);
+  const int N = C.N;
+  int64_t* const cnt = st->cnt.as<int64_t>();
+  int64_t* const att_off = st->att_off.as<int64_t>();
+  int64_t* const red = st->red.as<int64_t>();
+  ST_TRY(scan_list(st, s, cnt, att_off, N + 1));
+  ST_TRY(with_tmp(st, s, [&](void* t, size_t& ts) {
+    return hipcub::DeviceReduce::Sum(t, ts, st->cnt_leaves.as<int64_t>(), red, N + 1, s);
+  }));
+  // largest contig (a reduction, not one global atomic per contig: those serialise)
+  ST_TRY(with_tmp(st, s, [&](void* t, size_t& ts) { return hipcub::DeviceReduce::Max(t, ts, cnt, red + 1, N + 1, s); }));
+  if (C.level0) {
+    const int32_t* pend = st->pend.as<int32_t>();
+    ST_TRY(select_list(st, s, pend, st->act0.as<int32_t>(), red + 2, N));
+    int32_t *act_l0 = nullptr, *act1 = nullptr;
+    int64_t *base0 = nullptr, *base1 = nullptr;
+    ST_TRY(take(st->act_l0, s, N, act_l0));
+    ST_TRY(take(st->act1, s, N, act1));
+    ST_TRY(take(st->base0, s, (size_t)N + 1, base0));
+    ST_TRY(take(st->base1, s, (size_t)N + 1, base1));
+    using PendIt = hipcub::TransformInputIterator<bool, PendIs, const int32_t*>;
+    ST_TRY(select_list(st, s, PendIt(pend, PendIs{1}), act_l0, red + 4, N));
+    ST_TRY(select_list(st, s, PendIt(pend, PendIs{2}), act1, red + 5, N));
+    using AttIt = hipcub::TransformInputIterator<int64_t, ListAtt, hipcub::CountingInputIterator<int>>;
+    const hipcub::CountingInputIterator<int> from0(0);
+    ST_TRY(scan_list(st, s, AttIt(from0, ListAtt{act_l0, cnt, red + 4}), base0, N + 1));
+    ST_TRY(scan_list(st, s, AttIt(from0, ListAtt{act1, cnt, red + 5}), base1, N + 1));
+    hipLaunchKernelGGL(k_seed_info, dim3(1), dim3(64), 0, s, red, base0, base1, N);
+    ST_TRY(hipGetLastError());
+  }
+  unsigned long long* const hc = st->host_counters;   // pinned: [2] attachments, [3..10] red[0..7]
+  ST_TRY(read_counts(st, s, att_off + N, 1, red, 8, hc + 2));
+  C.A = (int64_t)hc[2]; C.TLB = (int64_t)hc[3]; C.max_att = (int64_t)hc[4];
+  C.n_first = C.level0 ? (int)hc[5] : N;            // contigs handed over (their attachments)
+  C.n_l0 = C.level0 ? (int)hc[7] : N;
+  C.n_seed = C.level0 ? (int)hc[8] : 0;
+  C.keys_l0 = (int64_t)(C.level0 ? hc[9] : hc[2]);
+  C.keys_seed = C.level0 ? (int64_t)hc[10] : 0;
+  return 0;
+}
+
+// Phase 3: the sort route of this call, every buffer of the levels sized from the counts and
+// wired into the kernel arguments, and hipcub's temp storage for every primitive of the levels
+// (sized once: no reallocation between enqueued kernels).
+static int size_buffers(Call& C) {
+  CALL_LOCALS(C);
+  SArgs& sa = C.sa;
+  const int N = C.N;
+  // per-contig LDS sort when every contig's attachments fit one workgroup's LDS (else a
+  // device radix sort of the whole level)
+  sa.sort_cap = 0;
+  if (C.max_att <= kSortMax && sa.key_tb + sa.key_lb + kSortIdxBits <= 64) {
+    sa.sort_cap = 2;
+    while (sa.sort_cap < C.max_att) sa.sort_cap <<= 1;
+  } else if (C.max_att <= kRadixMax && sa.key_tb + sa.key_lb <= 32) {
+    sa.sort_cap = (int)((C.max_att + 511) & ~int64_t(511));   // the LDS radix sort (k_sort_radix)
+  }
+  if (C.A >= st->att_limit || C.TLB >= (int64_t(1) << 31) - 1) {
+    *err = "too many hit-locus attachments for one batch (split it)";
+    return WF_E_TOOBIG;
+  }
+  const size_t A1 = (size_t)std::max<int64_t>(C.A, 1), T1 = (size_t)std::max<int64_t>(C.TLB, 1);
+  const size_t N1 = (size_t)N + 1;
+  ST_TRY(take(st->att_lo, s, A1, sa.att_lo));
+  ST_TRY(take(st->att_hi, s, A1, sa.att_hi));
+  ST_TRY(take(st->att_loc, s, A1, sa.att_loc));
+  ST_TRY(take(st->att_clade, s, A1, sa.att_clade));
+  ST_TRY(take(st->att_hit, s, A1, sa.att_hit));
+  ST_TRY(take(st->att_sc, s, A1, sa.att_sc));
+  ST_TRY(st->keys0.ensure(s, A1 * 8)); ST_TRY(st->keys1.ensure(s, A1 * 8));   // (sa.keys, sa.vals: the
+  ST_TRY(st->vals0.ensure(s, A1 * 4)); ST_TRY(st->vals1.ensure(s, A1 * 4));   // level's sorted pair)
+  ST_TRY(take(st->flags, s, A1, sa.flags));
+  ST_TRY(take(st->seg_id, s, A1, sa.seg_id));
+  ST_TRY(take(st->seg_start, s, A1 + 1, sa.seg_start));
+  ST_TRY(take(st->seg_crank, s, A1, sa.seg_crank));
+  ST_TRY(take(st->seg_mean, s, A1, sa.seg_mean));
+  ST_TRY(take(st->seg_nleaf, s, A1 + 1, sa.seg_nleaf));
+  ST_TRY(take(st->leaf_off, s, A1 + 1, sa.leaf_off));
+  ST_TRY(take(st->leaf_seg, s, T1, sa.leaf_seg));
+  ST_TRY(take(st->leaf_val, s, T1, sa.leaf_val));
+  ST_TRY(take(st->seg_rec, s, A1, sa.seg_rec));
+  ST_TRY(take(st->seg_cg, s, A1, sa.seg_cg));
+  ST_TRY(take(st->wave_list, s, A1, sa.wave_list));
+  ST_TRY(take(st->crank_first, s, N1, sa.crank_first));
+  ST_TRY(take(st->seg_cnt, s, N1, sa.seg_cnt));
+  ST_TRY(take(st->seg_len, s, A1, sa.seg_len));
+  if (sa.sort_cap == 0) sa.seg_len = nullptr;          // (k_seg_build writes it: not on the radix path)
+  ST_TRY(take(st->satt_lohi, s, A1, sa.satt_lohi));
+  ST_TRY(take(st->satt_sc, s, A1, sa.satt_sc));
+  ST_TRY(st->act0.ensure(s, (size_t)N * 4)); ST_TRY(st->act1.ensure(s, (size_t)N * 4));   // (wired per
+  ST_TRY(st->base0.ensure(s, N1 * 8)); ST_TRY(st->base1.ensure(s, N1 * 8));               // level)
+  // (rank, contig) pairs: k_one's hand-overs (one_list the whole level, two_list explain_two: the
+  // dense workgroup k_decide; big_list: k_big_sparse) and what k_big_sparse declines
+  ST_TRY(take(st->big_list, s, (size_t)N * 2, sa.big_list));
+  ST_TRY(take(st->big2_list, s, (size_t)N * 2, sa.big2_list));
+  ST_TRY(take(st->two_list, s, (size_t)N * 2, sa.two_list));
+  ST_TRY(take(st->one_list, s, (size_t)N * 2, sa.one_list));
+  const int64_t n_annot = C.NL * sa.k.n_sys;
+  if (n_annot > 0) ST_TRY(st->annot_best.ensure(s, (size_t)n_annot * 8));
+  sa.annot_best = st->annot_best.as<uint64_t>();
+  if (C.det) {                                         // --write-details only
+    ST_TRY(st->span_cnt.ensure(s, A1 * 4));
+    ST_TRY(st->spans.ensure(s, A1 * 8));
+  }
+  size_t t1 = 0, t2 = 0, t3 = 0, t4 = 0;
+  hipcub::DoubleBuffer<uint64_t> kb0(st->keys0.as<uint64_t>(), st->keys1.as<uint64_t>());
+  hipcub::DoubleBuffer<int32_t> vb0(st->vals0.as<int32_t>(), st->vals1.as<int32_t>());
+  ST_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, t1, kb0, vb0, (int)A1, 0, 64, s));
+  ST_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, t2, sa.flags, sa.seg_id, (int)A1, s));
+  ST_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, t3, sa.seg_nleaf, sa.leaf_off, (int)A1 + 1, s));
+  ST_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, t4, sa.seg_cnt, sa.crank_first, N + 1, s));
+  ST_TRY(st->tmp.ensure(s, std::max(std::max(t1, t4), std::max(t2, t3))));
+  return 0;
+}
+
+// The attachments of the C.n_first contigs (k_att_contig<1>), with the annotation transfer.
+static int attach(Call& C) {
+  CALL_LOCALS(C);
+  SArgs& sa = C.sa;
+  const int64_t n_annot = C.NL * sa.k.n_sys;
+  if (n_annot > 0 && (int64_t)C.max_loci * sa.k.n_sys > kAnnSlots) {   // HBM annotation slots
+    ST_TRY(hipMemsetAsync(st->annot_best.p, 0, (size_t)n_annot * 8, s));
+    ST_TRY(hipMemsetAsync(sa.k.annot, 0xFF, (size_t)n_annot * 4, s));     // -1: no winner
+  }
+  const int32_t* list = C.level0 ? st->act0.as<int32_t>() : nullptr;
+  const dim3 grid(std::min<unsigned>(C.agrid, (unsigned)C.n_first));
+  if (C.max_hits >= kAttBigHits)
+    hipLaunchKernelGGL((k_att_contig<1, kAttNTBig>), grid, dim3(kAttNTBig), 0, s, sa, nullptr, nullptr, nullptr, list,
+                       C.n_first);
+  else
+    hipLaunchKernelGGL((k_att_contig<1, kAttNT>), grid, dim3(kAttNT), 0, s, sa, nullptr, nullptr, nullptr, list,
+                       C.n_first);
+  ST_TRY(hipGetLastError());
+  return 0;
+}
+
+// Phase 4, one level's segment front end: the level's (key, attachment) pairs sorted, equal
+// keys cut into segments, and every segment's exact mean.  Three sort routes, chosen once per
+// call from the largest contig (sa.sort_cap):
+//   * at most kSortMax attachments: bitonic in LDS, a workgroup per contig (k_sort_contig);
+//   * up to kRadixMax (the cfg5 stress contigs): radix in LDS, a workgroup per contig -- the
+//     whole front end in one launch (k_front_radix), or k_sort_radix and the segment kernels
+//     below under --write-details, which reads the keys and sorted attachments back;
+//   * more (sort_cap 0): the device radix sort of the whole level.
+// and two segment routes after the sort: from per-contig segment counts (k_seg_build[_wide],
+// the LDS sorts) or from flags over the whole level (the device sort).
+static int level_segments(Call& C, int level, int n_act, int64_t n_keys) {
+  CALL_LOCALS(C);
+  SArgs& sa = C.sa;
+  const int end_bit = bits_for(n_act) + sa.key_tb + sa.key_lb;
+  if (end_bit > 64) { *err = "sort key wider than 64 bits"; return -1; }
+  hipcub::DoubleBuffer<uint64_t> kbuf(st->keys0.as<uint64_t>(), st->keys1.as<uint64_t>());
+  hipcub::DoubleBuffer<int32_t> vbuf(st->vals0.as<int32_t>(), st->vals1.as<int32_t>());
+  sa.keys = nullptr;
+  sa.vals = nullptr;
+  const unsigned leaf_grid = (unsigned)st->cus * 8u;   // k_leaf: persistent, 8 blocks per CU
+  const int t_seg = t_mark(st, s);
+  if (n_keys > 0 && sa.sort_cap > kSortMax && !C.det) {
+    // the stress contigs' whole front end in one launch (k_front_radix), then the rare
+    // wave / leaf segments it listed
+    static const hipError_t fattr = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_front_radix<false>),
+                                                        hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                        (int)radix_lds(kRadixMax));
+    static const hipError_t pattr = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_front_radix<true>),
+                                                        hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                        (int)radix_lds(kRadixMax, true));
+    ST_TRY(fattr);
+    ST_TRY(pattr);
+    const bool packed = sa.key_lb <= 6 && C.n_tax <= kPackTaxMax;
+    const size_t fr_bytes = ((size_t)n_act + 4) * sizeof(unsigned long long);
+    ST_TRY(st->front.ensure(s, fr_bytes));
+    ST_TRY(hipMemsetAsync(st->front.p, 0, fr_bytes, s));
+    unsigned long long* fr = st->front.as<unsigned long long>();
+    const size_t lds = radix_lds(sa.sort_cap, packed);
+    const int per_cu = std::max(1, (int)((160 * 1024) / (lds + 1024)));   // (+ its static LDS)
+    if (packed)
+      hipLaunchKernelGGL(k_front_radix<true>, dim3(std::min(n_act, st->cus * per_cu)), dim3(kRadixNT), lds, s, sa,
+                         n_act, n_keys, C.n_tax, fr);
+    else
+      hipLaunchKernelGGL(k_front_radix<false>, dim3(std::min(n_act, st->cus * per_cu)), dim3(kRadixNT), lds, s, sa,
+                         n_act, n_keys, C.n_tax, fr);
+    hipLaunchKernelGGL(k_front_fin, dim3(1), dim3(64), 0, s, sa, n_act, fr);
+    hipLaunchKernelGGL(k_seg_wave, dim3(st->cus * 32), dim3(64), 0, s, sa);
+    hipLaunchKernelGGL(k_leaf, dim3(leaf_grid), dim3(256), 0, s, sa, n_keys);
+    hipLaunchKernelGGL(k_seg_combine, dim3(st->cus * 4), dim3(256), 0, s, sa, n_keys);
+    ST_TRY(hipGetLastError());
+  } else if (n_keys > 0) {
+    if (sa.sort_cap > kSortMax) {
+      static const hipError_t rattr = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sort_radix),
+                                                          hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                          (int)radix_lds(kRadixMax));
+      ST_TRY(rattr);
+      const size_t lds = radix_lds(sa.sort_cap);
+      const int per_cu = std::max(1, (int)((160 * 1024) / lds));
+      hipLaunchKernelGGL(k_sort_radix, dim3(std::min(n_act, st->cus * per_cu)), dim3(kRadixNT), lds, s, sa, n_act,
+                         level, kbuf.Current(), vbuf.Current());
+    } else if (sa.sort_cap > 0) {
+      const size_t lds = (size_t)sa.sort_cap * 8;
+      const int per_cu = std::min(32, std::max(1, (int)((160 * 1024) / lds)));
+      // level 0: one wave per contig (10^4+ contigs fill the chip); later levels have
+      // few contigs, so four waves shorten each contig's sort
+      if (level == 0)
+        hipLaunchKernelGGL(k_sort_contig<64>, dim3(std::min(n_act, st->cus * per_cu)), dim3(64), lds, s,
+                           sa, n_act, level, kbuf.Current(), vbuf.Current());
+      else
+        hipLaunchKernelGGL(k_sort_contig<256>, dim3(std::min(n_act, st->cus * per_cu)), dim3(256), lds,
+                           s, sa, n_act, level, kbuf.Current(), vbuf.Current());
+    } else {
+      hipLaunchKernelGGL(k_keys_active, dim3(std::min(n_act, st->cus * 8)), dim3(256), 0, s, sa,
+                         n_act, kbuf.Current(), vbuf.Current());
+      ST_TRY(hipGetLastError());
+      ST_TRY(with_tmp(st, s, [&](void* t, size_t& ts) {
+        return hipcub::DeviceRadixSort::SortPairs(t, ts, kbuf, vbuf, (int)n_keys, 0, end_bit, s);
+      }));
+    }
+    ST_TRY(hipGetLastError());
+    sa.keys = kbuf.Current();
+    sa.vals = vbuf.Current();
+    if (sa.sort_cap > 0) {
+      if (n_act < 32 * kScanNT)        // <= 32 items a thread: one workgroup
+        hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(kScanNT), 0, s, sa.seg_cnt, sa.crank_first, n_act + 1);
+      else
+        ST_TRY(scan_list(st, s, sa.seg_cnt, sa.crank_first, n_act + 1));
+      if (sa.sort_cap > kSortMax)                   // (the radix-sorted stress contigs)
+        hipLaunchKernelGGL(k_seg_build_wide, dim3(std::min(n_act, st->cus * 4)), dim3(kRadixNT), 0, s, sa, n_act,
+                           level, n_keys);
+      else
+        hipLaunchKernelGGL(k_seg_build, dim3(std::min(n_act, st->cus * 32)), dim3(64), 0, s, sa, n_act,
+                           level, n_keys);
+    } else {
+      hipLaunchKernelGGL(k_seg_flags, dim3(grid_for(n_keys)), dim3(256), 0, s, sa, n_keys);
+      ST_TRY(with_tmp(st, s, [&](void* t, size_t& ts) {
+        return hipcub::DeviceScan::InclusiveSum(t, ts, sa.flags, sa.seg_id, (int)n_keys, s);
+      }));
+      hipLaunchKernelGGL(k_segs, dim3(grid_for(n_keys)), dim3(256), 0, s, sa, n_keys);
+      hipLaunchKernelGGL(k_gather, dim3(grid_for(n_keys)), dim3(256), 0, s, sa, n_keys);
+      hipLaunchKernelGGL(k_crank_first, dim3(grid_for(n_keys + 1)), dim3(256), 0, s, sa, n_keys, n_act);
+    }
+    if (C.det)
+      hipLaunchKernelGGL(k_seg_spans, dim3(grid_for(n_keys)), dim3(256), 0, s, sa, n_keys,
+                         st->span_cnt.as<int32_t>(), st->spans.as<int32_t>());
+    // short segments' means by one thread each; one wave per multi-attachment segment, a
+    // serial envelope sweep (62 VGPRs, 2.8 KB LDS -> 32 waves per CU; roll-up levels have
+    // ~10^5 such segments); the rest through the leaf kernels
+    hipLaunchKernelGGL(k_seg_rec, dim3(grid_for(n_keys + 1)), dim3(256), 0, s, sa, n_keys);
+    hipLaunchKernelGGL(k_seg_wave, dim3(st->cus * 32), dim3(64), 0, s, sa);
+    ST_TRY(scan_list(st, s, sa.seg_nleaf, sa.leaf_off, (int)n_keys + 1));
+    hipLaunchKernelGGL(k_leaf_expand, dim3(grid_for(n_keys)), dim3(256), 0, s, sa, n_keys);
+    hipLaunchKernelGGL(k_leaf, dim3(leaf_grid), dim3(256), 0, s, sa, n_keys);
+    hipLaunchKernelGGL(k_seg_combine, dim3(st->cus * 4), dim3(256), 0, s, sa, n_keys);
+    ST_TRY(hipGetLastError());
+  }
+  sa.keys = kbuf.Current();
+  sa.vals = vbuf.Current();
+  t_span(st, WF_PHASE_SEGMENTS, t_seg, t_mark(st, s));
+  return 0;
+}
+
+// Phase 5, one level's decisions: explain_one by one wave per contig (k_one); the dense
+// workgroup (k_decide) for the contigs of more than 63 loci it hands over or leaves open;
+// the segment-table decision (k_big_sparse) for the others it hands over, and the dense
+// decision in an HBM slot (k_decide_big) for what that declines.  n_act and n_keys become the
+// next level's: the contigs raised here and their attachments.
+static int level_decide(Call& C, int level, bool first_level, int& n_act, int64_t& n_keys) {
+  CALL_LOCALS(C);
+  SArgs& sa = C.sa;
+  unsigned long long* const hcnt = st->host_counters;
+  const int t_dec = t_mark(st, s);
+  const unsigned dgrid = (unsigned)std::min<int64_t>(n_act, (int64_t)st->cus * 16);
+  hipLaunchKernelGGL(k_one, dim3(std::min<int64_t>(n_act, (int64_t)st->cus * 32)), dim3(64), 0, s, sa,
+                     n_act, level, n_keys);
+  // the dense decision for what k_one handed over whole (> 63 loci, more segments than it
+  // holds, --weak-loci assign-unknown) and the > 63-loci contigs it left open
+  // (counts on the device: a grid of rank-independent size, idle blocks exit at once): as many
+  // one-wave workgroups as the arena and 3 waves/SIMD (VGPRs) allow
+  const unsigned dec_per_cu =
+      (unsigned)std::max<int64_t>(1, std::min<int64_t>(12, (160 * 1024) / std::max<int64_t>(st->dec_lds, 1)));
+  hipLaunchKernelGGL(k_decide, dim3(std::min<unsigned>(dgrid, (unsigned)st->cus * dec_per_cu)), dim3(kDecNT),
+                     (size_t)st->dec_lds, s, sa, level, n_keys);
+  ST_TRY(hipGetLastError());
+  t_span(st, WF_PHASE_DECIDE, t_dec, t_mark(st, s));
+  ST_TRY(read_counts(st, s, sa.counters, 5, nullptr, 0, hcnt));
+  if (hcnt[4]) {                                     // (k_front_radix's look-back never completed)
+    *err = "segment look-back timed out";
+    return -2;
+  }
+  const int n_big = (int)hcnt[2];
+  int n_dense = 0;                      // contigs that need the dense decision in an HBM slot
+  const int t_big = n_big > 0 ? t_mark(st, s) : -1;
+  if (n_big > 0) {
+    // the decision from the segment table, one wave per contig (wf_sparse.h): as many
+    // waves as are resident at once (LDS-bound)
+    const int grid = std::min(n_big, st->cus * sparse_waves(st));
+    ST_TRY(take(st->sp_ws, s, (size_t)grid * kSpSlot, sa.sp_ws));
+    hipLaunchKernelGGL(k_big_sparse, dim3(grid), dim3(64), 0, s, sa, level, n_keys);
+    ST_TRY(hipGetLastError());
+    ST_TRY(read_counts(st, s, sa.counters, 4, nullptr, 0, hcnt));
+    n_dense = (int)hcnt[1];
+  }
+  if (n_dense > 0) {
+    const int64_t slot = ((int64_t)hcnt[3] + 255) & ~int64_t(255);
+    // HBM-slot workgroups: as many as are resident at once (135 VGPRs: 3 four-wave
+    // workgroups per CU); cfg5 (30 k stress contigs, round 2) measured 234.7 ms/pass at 2
+    // per CU, 222.8 at 3, 264.5 at 4 (a second, partial round), 230.2 at 8
+    const int slots = std::min(n_dense, st->cus * 3);
+    ST_TRY(take(st->big_ws, s, (size_t)slot * slots, sa.k.big_ws));
+    sa.k.slot_bytes = slot;
+    hipLaunchKernelGGL(k_decide_big, dim3(slots), dim3(kBlock), 0, s, sa, level, n_keys);
+    ST_TRY(hipGetLastError());
+    ST_TRY(read_counts(st, s, sa.counters, 4, nullptr, 0, hcnt));
+  }
+  if (n_big > 0) t_span(st, WF_PHASE_BIG, t_big, t_mark(st, s));
+  if (first_level && !st->dec_lds_fixed && n_dense * 50 > n_act && st->dec_lds < 48 * 1024)
+    st->dec_lds += 8 * 1024;   // adaptive arena: grows while > 2% of a first level overflow
+  n_act = (int)(hcnt[0] >> 40);
+  n_keys = (int64_t)(hcnt[0] & ((1ull << 40) - 1));
+  return 0;
+}
+
+// The roll-up levels of the staged path: level 0 over the contigs handed over at pend 1 (or
+// every contig), level 1 beginning with the seeds (pend 2); each level's segments, then its
+// decisions, until no contig is raised.  Level L counts into block L of lvl_ctr; the host
+// reads the words after each level.
+static int run_levels(Call& C) {
+  CALL_LOCALS(C);
+  SArgs& sa = C.sa;
+  Buf* act[2] = {&st->act0, &st->act1};
+  Buf* base[2] = {&st->base0, &st->base1};
+  const int n_lv = kMaxIter + 2;
+  unsigned long long* lvl_ctr = nullptr;
+  ST_TRY(take(st->lvl_ctr, s, (size_t)n_lv * 8, lvl_ctr));
+  ST_TRY(hipMemsetAsync(lvl_ctr, 0, (size_t)n_lv * 8 * sizeof(unsigned long long), s));
+  int n_act = C.n_l0;
+  int64_t n_keys = C.keys_l0;
+  int start = 0;
+  if (C.n_seed > 0) {                   // level 1 begins with the seeds (level 0 appends)
+    hipLaunchKernelGGL(k_set_word, dim3(1), dim3(64), 0, s, lvl_ctr,
+                       ((unsigned long long)C.n_seed << 40) | (unsigned long long)C.keys_seed);
+    hipLaunchKernelGGL(k_rekey_seeds, dim3(std::min(C.n_seed, st->cus * 8)), dim3(256), 0, s, st->act1.as<int32_t>(),
+                       C.n_seed, sa.catt_off, sa.att_clade, sa.k.parent);
+    ST_TRY(hipGetLastError());
+    if (C.n_l0 == 0) {
+      start = 1;
+      n_act = C.n_seed;
+      n_keys = C.keys_seed;
+    }
+  }
+  if (C.det) C.det->levels.clear();
+  if (st->dec_lds > 64 * 1024) {
+    // per process, thread-safe initialisation (C++11 statics); every device is a gfx950
+    static const hipError_t attr3 = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decide),
+                                                        hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                        160 * 1024 - 1024);
+    ST_TRY(attr3);
+  }
+  for (int level = start; n_act > 0 && level <= kMaxIter; ++level) {
+    sa.counters = lvl_ctr + 8 * level;
+    const int cur = level & 1;
+    sa.act = level == 0 ? (C.level0 ? st->act_l0.as<int32_t>() : nullptr) : act[cur]->as<int32_t>();
+    sa.act_base = level == 0 && !C.level0 ? nullptr : base[cur]->as<int64_t>();
+    sa.act_next = act[cur ^ 1]->as<int32_t>();
+    sa.act_base_next = base[cur ^ 1]->as<int64_t>();
+    int rc = level_segments(C, level, n_act, n_keys);
+    if (rc) return rc;
+    if (C.det) ST_TRY(details_level(st, sa, level, n_act, n_keys, s, C.det));
+    rc = level_decide(C, level, level == start, n_act, n_keys);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+// Runs the whole path for one batch on stream `s` (synchronising on it between levels).
+// `k` carries device pointers for batch, taxonomy, params and results.
 static int staged_run(StagedState* st, const KArgs& k, int n_tax, int max_loci, int max_hits, int64_t NH,
                       int64_t NL, hipStream_t s, std::string* err, DetailsSink* det) {
   const int N = k.n_contigs;
@@ -2211,10 +2728,10 @@ static int staged_run(StagedState* st, const KArgs& k, int n_tax, int max_loci, 
   }
   int rc = build_lut(st, s, err);
   if (rc) return rc;
-  int64_t* hc = reinterpret_cast<int64_t*>(st->host_counters);   // pinned
   if (NH >= (int64_t(1) << 31) - 1) { *err = "too many hits for one batch (split it)"; return -1; }
 
-  SArgs sa{};
+  Call C{st, s, err, det, N, n_tax, max_loci, max_hits, NH, NL};
+  SArgs& sa = C.sa;
   sa.k = k;
   sa.n_hits_i = (int)NH;
   sa.key_lb = bits_for(std::max(max_loci, 1));
@@ -2223,560 +2740,33 @@ static int staged_run(StagedState* st, const KArgs& k, int n_tax, int max_loci, 
   sa.lut = st->lut.as<int4>();
   sa.dec_lds_bytes = st->dec_lds;
   sa.force_big = st->sparse_big == 2 ? 1 : 0;
-  sa.route_sparse = st->sparse_big >= 2 ? 1 : 0;
-  sa.sparse_on = st->sparse_big != 0 ? 1 : 0;
   // kernels take SArgs by value (kernarg segment): no argument uploads, and the pointers
   // loaded from it are known to be global (global_* instead of flat_* memory operations)
-  ST_TRY(st->counters.ensure(s, 8 * sizeof(unsigned long long)));
-  sa.counters = st->counters.as<unsigned long long>();
-
-  // contigs, hits -> attachments (per-contig counts, offsets, then the attachments)
+  ST_TRY(take(st->counters, s, 8, sa.counters));
+  // per-contig attachment and leaf counts, attachment offsets, the reductions' results
   ST_TRY(st->cnt.ensure(s, (size_t)(N + 1) * sizeof(int64_t)));
   ST_TRY(st->cnt_leaves.ensure(s, (size_t)(N + 1) * sizeof(int64_t)));
-  ST_TRY(st->att_off.ensure(s, (size_t)(N + 1) * sizeof(int64_t)));
+  ST_TRY(take(st->att_off, s, (size_t)N + 1, sa.catt_off));
   ST_TRY(st->red.ensure(s, 8 * sizeof(int64_t)));
-  sa.catt_off = st->att_off.as<int64_t>();
-  const unsigned agrid = (unsigned)std::min<int64_t>(N, (int64_t)st->cus * 32);   // waves per CU
+  C.agrid = (unsigned)std::min<int64_t>(N, (int64_t)st->cus * 32);
   ST_TRY(hipMemsetAsync(st->red.p, 0, 8 * sizeof(int64_t), s));
   ST_TRY(hipMemsetAsync(st->cnt.as<int64_t>() + N, 0, sizeof(int64_t), s));
   ST_TRY(hipMemsetAsync(st->cnt_leaves.as<int64_t>() + N, 0, sizeof(int64_t), s));
   // Fused level 0 (wf_fast.hip) unless --write-details (per-level records of every contig)
   // or HBM annotation slots are needed.
   // (the wave kernels' 32-bit keys hold clade ids below 2^17)
-  const bool level0 = st->level0 && !det && (int64_t)max_loci * k.n_sys <= kAnnSlots && sa.key_tb <= 17;
+  C.level0 = st->level0 && !det && (int64_t)max_loci * k.n_sys <= kAnnSlots && sa.key_tb <= 17;
   hipLaunchKernelGGL(k_init, dim3(grid_for(N)), dim3(256), 0, s, sa.k);
-  int t_waves = level0 ? t_mark(st, s) : -1;          // (the waves span: the wave launches alone)
-  if (level0) {
-    ST_TRY(st->pend.ensure(s, (size_t)N * 4));
-    ST_TRY(st->act0.ensure(s, (size_t)N * 4));
-    // The first form hands the contigs it leaves at explain_two (or at an unproven
-    // assign-unknown row) over with their level-0 segment tables, every mean evaluated:
-    // k_dump_sparse decides them from the table (pend 3 -> 0, 2 or 1)
-    const bool dump = st->sparse_big != 0 && !st->rollup;
-    // Wave levels: the first form also decides explain_two and carries the roll-up levels,
-    // one launch per level over the contigs the level before raised
-    const bool levels = dump;
-    SArgs da = sa;
-    unsigned long long* rcnt = nullptr;              // [kMaxIter + 2] per-level list counts, fail count
-    if (dump) {
-      int64_t cap = std::min<int64_t>(std::max<int64_t>((int64_t)N * 32, 1 << 16), (1ll << 31) - 4096);
-      if (st->dump_cap > 0) cap = st->dump_cap;      // WF_OPT_DUMP_CAP (tests: the overflow branch)
-      ST_TRY(st->dump_cg.ensure(s, (size_t)cap * 8)); ST_TRY(st->dump_mean.ensure(s, (size_t)cap * 8));
-      ST_TRY(st->dump_first.ensure(s, ((size_t)N + 1) * 4)); ST_TRY(st->dump_list.ensure(s, (size_t)N * 8));
-      ST_TRY(st->dump_ctr.ensure(s, 16));
-      ST_TRY(hipMemsetAsync(st->dump_ctr.p, 0, 16, s));
-      da.dump_cap = cap;
-      da.dump_cg = st->dump_cg.as<int2>(); da.dump_mean = st->dump_mean.as<double>();
-      da.dump_first = st->dump_first.as<int32_t>(); da.dump_list = st->dump_list.as<int32_t>();
-      da.dump_ctr = st->dump_ctr.as<unsigned long long>();
-      if (levels) {
-        ST_TRY(st->dump_um.ensure(s, (size_t)N * 8));
-        da.dump_um = st->dump_um.as<uint64_t>();
-        ST_TRY(st->roll0.ensure(s, (size_t)N * 4)); ST_TRY(st->roll1.ensure(s, (size_t)N * 4));
-        ST_TRY(st->roll_cnt.ensure(s, (kMaxIter + 3) * sizeof(unsigned long long)));
-        ST_TRY(st->anc.ensure(s, (size_t)std::max(n_tax, 1) * 4));
-        ST_TRY(hipMemsetAsync(st->roll_cnt.p, 0, (kMaxIter + 3) * sizeof(unsigned long long), s));
-        rcnt = st->roll_cnt.as<unsigned long long>();
-        da.n_tax = n_tax;
-        da.wave_two = st->wave_two;
-        da.roll_next = st->roll1.as<int32_t>();     // level L appends to roll[(L + 1) & 1]
-        da.roll_next_n = rcnt + 1;
-        da.fail_ctr = rcnt + kMaxIter + 2;
-      }
-    }
-    if (levels || st->triage) {
-      // work queues: [0] the level-0 list, [L] level L's launch
-      ST_TRY(st->wq.ensure(s, (kMaxIter + 2) * sizeof(unsigned long long)));
-      ST_TRY(hipMemsetAsync(st->wq.p, 0, (kMaxIter + 2) * sizeof(unsigned long long), s));
-    }
-    if (st->triage) {
-      // the triage (wf_triage.hip) decides the contigs explain_one settles from their full
-      // clades; the first wave form runs the rest from its list (count on the device)
-      ST_TRY(st->tri_list.ensure(s, (size_t)N * 4));
-      ST_TRY(st->tri_cnt.ensure(s, 8));
-      if (!da.k.hkey) {                                  // no wf_batch.hit_key: packed here
-        ST_TRY(st->hkey.ensure(s, (size_t)std::max<int64_t>(NH, 1) * 4));
-        ST_TRY(pack_keys(da.k, NH, st->hkey.as<uint32_t>(), st->cus, s));
-        da.k.hkey = st->hkey.as<uint32_t>();
-        sa.k.hkey = da.k.hkey;                         // (k_att_contig reads it too)
-      }
-      const int t_tri0 = t_mark(st, s);                 // (the triage span: its launch alone)
-      ST_TRY(launch_triage(da, st->cnt.as<int64_t>(), st->cnt_leaves.as<int64_t>(), st->pend.as<int32_t>(), max_hits,
-                           st->cus, s));
-      const int t_tri = t_mark(st, s);
-      t_span(st, WF_PHASE_WAVES, t_waves, t_tri0);
-      t_span(st, WF_PHASE_TRIAGE, t_tri0, t_tri);
-      t_waves = t_tri;
-      using PendItT = hipcub::TransformInputIterator<bool, PendIs, const int32_t*>;
-      ST_TRY(select_list(st, s, PendItT(st->pend.as<int32_t>(), PendIs{kPendTriage}), st->tri_list.as<int32_t>(),
-                         st->tri_cnt.as<int64_t>(), N));
-      SArgs ta = da;                                   // (the list's contigs vary in cost as the roll-up lists')
-      ta.wq = st->wq.as<unsigned long long>();
-      ST_TRY(launch_fast_list(ta, st->cnt.as<int64_t>(), st->cnt_leaves.as<int64_t>(), st->pend.as<int32_t>(),
-                              st->tri_list.as<int32_t>(), st->tri_cnt.as<int64_t>(), max_hits, st->cus, s));
-    } else {
-      ST_TRY(launch_fast(da, st->cnt.as<int64_t>(), st->cnt_leaves.as<int64_t>(), st->pend.as<int32_t>(), max_hits,
-                         st->cus, s));
-    }
-    if (dump) {
-      const int t_h0 = t_mark(st, s);
-      t_span(st, WF_PHASE_WAVES, t_waves, t_h0);
-      const int grid = st->cus * sparse_waves(st);
-      ST_TRY(st->sp_ws.ensure(s, (size_t)grid * kSpSlot));
-      da.sp_ws = st->sp_ws.as<char>();
-      da.seg_cg = da.dump_cg; da.seg_mean = da.dump_mean; da.crank_first = da.dump_first;
-      da.seed_pend = st->pend.as<int32_t>();
-      if (levels) {
-        da.anc = st->anc.as<int32_t>();               // (k_dump_sparse: ancestors of level 1)
-        da.dump_ctr_next = da.dump_ctr + 1;
-      }
-      const int grid2 = st->cus * two_waves(st);
-      if (levels)                                       // compact tables (and the level set-up)
-        hipLaunchKernelGGL(k_dump_sparse<1>, dim3(grid2), dim3(64), 0, s, da, st->cnt.as<int64_t>(),
-                           st->cnt_leaves.as<int64_t>(), 0);
-      hipLaunchKernelGGL(k_dump_sparse<0>, dim3(grid), dim3(64), 0, s, da, st->cnt.as<int64_t>(),
-                         st->cnt_leaves.as<int64_t>(), 0);
-      ST_TRY(hipGetLastError());
-      const int t_h1 = t_mark(st, s);
-      t_span(st, WF_PHASE_HANDOVER, t_h0, t_h1);
-      t_waves = t_h1;                                  // the waves span resumes here
-      if (levels) {
-        // levels 1, 2, ...: enqueued kLevelChunk at a time (a level with an empty list costs two
-        // near-empty launches), then the next level's count is read back
-        constexpr int kLevelChunk = 5;
-        unsigned long long* dctr = st->dump_ctr.as<unsigned long long>();
-        int32_t* roll[2] = {st->roll0.as<int32_t>(), st->roll1.as<int32_t>()};
-        int L = 1;
-        unsigned long long* hcnt = st->host_counters;
-        for (;;) {
-          const int L_end = std::min(L + kLevelChunk - 1, kMaxIter);
-          for (; L <= L_end; ++L) {
-            SArgs la = da;
-            la.dump_ctr = dctr + (L & 1);
-            la.dump_ctr_next = dctr + ((L + 1) & 1);
-            la.roll_next = roll[(L + 1) & 1];
-            la.roll_next_n = rcnt + L + 1;
-            la.wq = st->wq.as<unsigned long long>() + L;
-            ST_TRY(launch_level(la, st->cnt.as<int64_t>(), st->cnt_leaves.as<int64_t>(), st->pend.as<int32_t>(),
-                                roll[L & 1], reinterpret_cast<const int64_t*>(rcnt + L), L, max_hits, st->cus, s));
-            la.wq = nullptr;                             // (a queue for sp_two: r5t, 0.35 ms slower)
-            hipLaunchKernelGGL(k_dump_sparse<1>, dim3(grid2), dim3(64), 0, s, la, st->cnt.as<int64_t>(),
-                               st->cnt_leaves.as<int64_t>(), L);
-            hipLaunchKernelGGL(k_dump_sparse<0>, dim3(grid), dim3(64), 0, s, la, st->cnt.as<int64_t>(),
-                               st->cnt_leaves.as<int64_t>(), L);
-            ST_TRY(hipGetLastError());
-          }
-          if (st->mbox) {
-            ST_TRY(publish_sync(st, s, rcnt + L, 1, rcnt + kMaxIter + 2, 1, hcnt));
-          } else {
-            ST_TRY(hipMemcpyAsync(hcnt, rcnt + L, 8, hipMemcpyDeviceToHost, s));
-            ST_TRY(hipMemcpyAsync(hcnt + 1, rcnt + kMaxIter + 2, 8, hipMemcpyDeviceToHost, s));
-            ST_TRY(spin_sync(s, st->lvl_ev[0]));
-          }
-          if (hcnt[0] == 0 || L > kMaxIter) break;
-        }
-        const int t_r1 = t_mark(st, s);
-        t_span(st, WF_PHASE_ROLLUP, t_h1, t_r1);
-        t_waves = t_r1;
-        if (hcnt[1] == 0) return 0;                    // every contig finished in the wave forms
-      }
-    }
-    // the other contigs it handed over (pend 1) through the second wave form, its list and
-    // count built on the device
-    // (only those whose attachments fit the second form's slice: the others would load every
-    // hit only to be handed on again)
-    using FitIt = hipcub::TransformInputIterator<bool, PendFits, hipcub::CountingInputIterator<int>>;
-    ST_TRY(select_list(st, s, FitIt(hipcub::CountingInputIterator<int>(0),
-                                    PendFits{st->pend.as<int32_t>(), st->cnt.as<int64_t>(), max_hits <= 256 ? 256 : 512}),
-                       st->act0.as<int32_t>(), st->red.as<int64_t>() + 3, N));
-    ST_TRY(launch_full(sa, st->cnt.as<int64_t>(), st->cnt_leaves.as<int64_t>(), st->pend.as<int32_t>(),
-                       st->act0.as<int32_t>(), st->red.as<int64_t>() + 3, max_hits, st->cus, st->rollup, s));
-  } else {
-    hipLaunchKernelGGL((k_att_contig<0, kAttNT>), dim3(agrid), dim3(kAttNT), 0, s, sa, st->cnt.as<int64_t>(),
-                       st->cnt_leaves.as<int64_t>(),
-                       reinterpret_cast<unsigned long long*>(st->red.as<int64_t>() + 1), nullptr, N);
-  }
-  ST_TRY(hipGetLastError());
-  t_span(st, WF_PHASE_WAVES, t_waves, t_mark(st, s));
-  const int t_attach = t_mark(st, s);
-  {
-    size_t t1 = 0, t2 = 0;
-    ST_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, t1, st->cnt.as<int64_t>(),
-                                            st->att_off.as<int64_t>(), (int)(N + 1), s));
-    ST_TRY(hipcub::DeviceReduce::Sum(nullptr, t2, st->cnt_leaves.as<int64_t>(),
-                                     st->red.as<int64_t>(), (int)(N + 1), s));
-    size_t t3 = 0, t4 = 0;
-    ST_TRY(hipcub::DeviceReduce::Max(nullptr, t3, st->cnt.as<int64_t>(), st->red.as<int64_t>() + 1,
-                                     (int)(N + 1), s));
-    if (level0)
-      ST_TRY(hipcub::DeviceSelect::Flagged(nullptr, t4, hipcub::CountingInputIterator<int32_t>(0),
-                                           st->pend.as<int32_t>(), st->act0.as<int32_t>(),
-                                           st->red.as<int64_t>() + 2, N, s));
-    ST_TRY(st->tmp.ensure(s, std::max(std::max(t1, t4), std::max(t2, t3))));
-    size_t tb = st->tmp.n;
-    ST_TRY(hipcub::DeviceScan::ExclusiveSum(st->tmp.p, tb, st->cnt.as<int64_t>(),
-                                            st->att_off.as<int64_t>(), (int)(N + 1), s));
-    tb = st->tmp.n;
-    ST_TRY(hipcub::DeviceReduce::Sum(st->tmp.p, tb, st->cnt_leaves.as<int64_t>(),
-                                     st->red.as<int64_t>(), (int)(N + 1), s));
-    // largest contig (a reduction, not one global atomic per contig: those serialise)
-    tb = st->tmp.n;
-    ST_TRY(hipcub::DeviceReduce::Max(st->tmp.p, tb, st->cnt.as<int64_t>(), st->red.as<int64_t>() + 1,
-                                     (int)(N + 1), s));
-    if (level0) {                     // the contigs k_fast handed over, in contig order
-      tb = st->tmp.n;
-      ST_TRY(hipcub::DeviceSelect::Flagged(st->tmp.p, tb, hipcub::CountingInputIterator<int32_t>(0),
-                                           st->pend.as<int32_t>(), st->act0.as<int32_t>(),
-                                           st->red.as<int64_t>() + 2, N, s));
-    }
-  }
-  if (level0) {
-    // staged level 0 list (pend 1) and level 1 seeds (pend 2), each with compact key bases
-    ST_TRY(st->act_l0.ensure(s, (size_t)N * 4)); ST_TRY(st->act1.ensure(s, (size_t)N * 4));
-    ST_TRY(st->base0.ensure(s, (size_t)(N + 1) * 8)); ST_TRY(st->base1.ensure(s, (size_t)(N + 1) * 8));
-    int64_t* red = st->red.as<int64_t>();
-    using PendIt = hipcub::TransformInputIterator<bool, PendIs, const int32_t*>;
-    const int32_t* pend = st->pend.as<int32_t>();
-    ST_TRY(select_list(st, s, PendIt(pend, PendIs{1}), st->act_l0.as<int32_t>(), red + 4, N));
-    ST_TRY(select_list(st, s, PendIt(pend, PendIs{2}), st->act1.as<int32_t>(), red + 5, N));
-    using AttIt = hipcub::TransformInputIterator<int64_t, ListAtt, hipcub::CountingInputIterator<int>>;
-    const int64_t* cnt = st->cnt.as<int64_t>();
-    ST_TRY(scan_list(st, s, AttIt(hipcub::CountingInputIterator<int>(0), ListAtt{st->act_l0.as<int32_t>(), cnt, red + 4}),
-                     st->base0.as<int64_t>(), N + 1));
-    ST_TRY(scan_list(st, s, AttIt(hipcub::CountingInputIterator<int>(0), ListAtt{st->act1.as<int32_t>(), cnt, red + 5}),
-                     st->base1.as<int64_t>(), N + 1));
-    hipLaunchKernelGGL(k_seed_info, dim3(1), dim3(64), 0, s, red, st->base0.as<int64_t>(), st->base1.as<int64_t>(), N);
-    ST_TRY(hipGetLastError());
-  }
-  const bool mailbox = st->mbox != nullptr;
-  if (mailbox) {
-    ST_TRY(publish_sync(st, s, st->att_off.as<int64_t>() + N, 1, st->red.p, 8,
-                        reinterpret_cast<unsigned long long*>(&hc[2])));
-  } else {
-    ST_TRY(hipMemcpyAsync(&hc[2], st->att_off.as<int64_t>() + N, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    ST_TRY(hipMemcpyAsync(&hc[3], st->red.p, 8 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    ST_TRY(spin_sync(s, st->lvl_ev[0]));
-  }
-  const int64_t A = hc[2], TLB = hc[3], max_att = hc[4];
-  const int n_first = level0 ? (int)hc[5] : N;     // contigs handed over (their attachments)
-  if (n_first == 0) return 0;                       // the wave kernels finished every contig
-  const int n_l0 = level0 ? (int)hc[7] : N, n_seed = level0 ? (int)hc[8] : 0;
-  const int64_t keys_l0 = level0 ? hc[9] : hc[2], keys_seed = level0 ? hc[10] : 0;
-  // per-contig LDS sort when every contig's attachments fit one workgroup's LDS (else a
-  // device radix sort of the whole level)
-  sa.sort_cap = 0;
-  if (max_att <= kSortMax && sa.key_tb + sa.key_lb + kSortIdxBits <= 64) {
-    sa.sort_cap = 2;
-    while (sa.sort_cap < max_att) sa.sort_cap <<= 1;
-  } else if (max_att <= kRadixMax && sa.key_tb + sa.key_lb <= 32) {
-    sa.sort_cap = (int)((max_att + 511) & ~int64_t(511));   // the LDS radix sort (k_sort_radix)
-  }
-  if (A >= st->att_limit || TLB >= (int64_t(1) << 31) - 1) {
-    *err = "too many hit-locus attachments for one batch (split it)";
-    return WF_E_TOOBIG;
-  }
-  const size_t A1 = (size_t)std::max<int64_t>(A, 1), T1 = (size_t)std::max<int64_t>(TLB, 1);
-  ST_TRY(st->att_lo.ensure(s, A1 * 4)); ST_TRY(st->att_hi.ensure(s, A1 * 4));
-  ST_TRY(st->att_loc.ensure(s, A1 * 4)); ST_TRY(st->att_clade.ensure(s, A1 * 4));
-  ST_TRY(st->att_hit.ensure(s, A1 * 4)); ST_TRY(st->att_sc.ensure(s, A1 * 8));
-  ST_TRY(st->keys0.ensure(s, A1 * 8)); ST_TRY(st->keys1.ensure(s, A1 * 8));
-  ST_TRY(st->vals0.ensure(s, A1 * 4)); ST_TRY(st->vals1.ensure(s, A1 * 4));
-  ST_TRY(st->flags.ensure(s, A1 * 4)); ST_TRY(st->seg_id.ensure(s, A1 * 4));
-  ST_TRY(st->seg_start.ensure(s, (A1 + 1) * 4)); ST_TRY(st->seg_crank.ensure(s, A1 * 4));
-  ST_TRY(st->seg_mean.ensure(s, A1 * 8));
-  ST_TRY(st->seg_nleaf.ensure(s, (A1 + 1) * 4)); ST_TRY(st->leaf_off.ensure(s, (A1 + 1) * 4));
-  ST_TRY(st->leaf_seg.ensure(s, T1 * 4)); ST_TRY(st->leaf_val.ensure(s, T1 * 8));
-  ST_TRY(st->seg_rec.ensure(s, A1 * 16)); ST_TRY(st->seg_cg.ensure(s, A1 * 8));
-  ST_TRY(st->wave_list.ensure(s, A1 * 4));
-  ST_TRY(st->crank_first.ensure(s, ((size_t)N + 1) * 4));
-  ST_TRY(st->seg_cnt.ensure(s, ((size_t)N + 1) * 4));
-  ST_TRY(st->satt_lohi.ensure(s, A1 * 8)); ST_TRY(st->satt_sc.ensure(s, A1 * 8));
-  ST_TRY(st->act0.ensure(s, (size_t)N * 4)); ST_TRY(st->act1.ensure(s, (size_t)N * 4));
-  ST_TRY(st->base0.ensure(s, (size_t)(N + 1) * 8)); ST_TRY(st->base1.ensure(s, (size_t)(N + 1) * 8));
-  ST_TRY(st->big_list.ensure(s, (size_t)N * 8));
-  ST_TRY(st->big2_list.ensure(s, (size_t)N * 8));
-  ST_TRY(st->two_list.ensure(s, (size_t)N * 8));
-  ST_TRY(st->one_list.ensure(s, (size_t)N * 8));
-  const int64_t n_annot = NL * k.n_sys;
-  if (n_annot > 0) ST_TRY(st->annot_best.ensure(s, (size_t)n_annot * 8));
-  {
-    // temp storage for every primitive of this call, sized once (no reallocation between
-    // enqueued kernels)
-    size_t t1 = 0, t2 = 0, t3 = 0;
-    hipcub::DoubleBuffer<uint64_t> kb0(st->keys0.as<uint64_t>(), st->keys1.as<uint64_t>());
-    hipcub::DoubleBuffer<int32_t> vb0(st->vals0.as<int32_t>(), st->vals1.as<int32_t>());
-    ST_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, t1, kb0, vb0, (int)A1, 0, 64, s));
-    ST_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, t2, st->flags.as<int32_t>(),
-                                            st->seg_id.as<int32_t>(), (int)A1, s));
-    ST_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, t3, st->seg_nleaf.as<int32_t>(),
-                                            st->leaf_off.as<int32_t>(), (int)A1 + 1, s));
-    size_t t4 = 0;
-    ST_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, t4, st->seg_cnt.as<int32_t>(),
-                                            st->crank_first.as<int32_t>(), N + 1, s));
-    ST_TRY(st->tmp.ensure(s, std::max(std::max(t1, t4), std::max(t2, t3))));
-  }
-  sa.att_lo = st->att_lo.as<int32_t>(); sa.att_hi = st->att_hi.as<int32_t>();
-  sa.att_loc = st->att_loc.as<int32_t>(); sa.att_clade = st->att_clade.as<int32_t>();
-  sa.att_hit = st->att_hit.as<int32_t>(); sa.att_sc = st->att_sc.as<double>();
-  sa.flags = st->flags.as<int32_t>(); sa.seg_id = st->seg_id.as<int32_t>();
-  sa.seg_start = st->seg_start.as<int32_t>(); sa.seg_crank = st->seg_crank.as<int32_t>();
-  sa.seg_mean = st->seg_mean.as<double>();
-  sa.seg_nleaf = st->seg_nleaf.as<int32_t>(); sa.leaf_off = st->leaf_off.as<int32_t>();
-  sa.leaf_seg = st->leaf_seg.as<int32_t>(); sa.leaf_val = st->leaf_val.as<double>();
-  sa.seg_rec = st->seg_rec.as<int4>();
-  sa.seg_cg = st->seg_cg.as<int2>();
-  sa.crank_first = st->crank_first.as<int32_t>();
-  sa.seg_cnt = st->seg_cnt.as<int32_t>();
-  ST_TRY(st->seg_len.ensure(s, A1 * 4));
-  sa.seg_len = sa.sort_cap > 0 ? st->seg_len.as<int32_t>() : nullptr;   // set by k_seg_build
-  sa.satt_lohi = st->satt_lohi.as<int2>(); sa.satt_sc = st->satt_sc.as<double>();
-  sa.annot_best = st->annot_best.as<uint64_t>();
-  sa.big_list = st->big_list.as<int32_t>();
-  sa.big2_list = st->big2_list.as<int32_t>();
-  sa.two_list = st->two_list.as<int32_t>();
-  sa.wave_list = st->wave_list.as<int32_t>();
-  if (n_annot > 0 && (int64_t)max_loci * k.n_sys > kAnnSlots) {   // HBM annotation slots
-    ST_TRY(hipMemsetAsync(st->annot_best.p, 0, (size_t)n_annot * 8, s));
-    ST_TRY(hipMemsetAsync(k.annot, 0xFF, (size_t)n_annot * 4, s));     // -1: no winner
-  }
-  if (max_hits >= kAttBigHits)
-    hipLaunchKernelGGL((k_att_contig<1, kAttNTBig>), dim3(std::min<unsigned>(agrid, (unsigned)n_first)), dim3(kAttNTBig), 0,
-                       s, sa, nullptr, nullptr, nullptr, level0 ? st->act0.as<int32_t>() : nullptr, n_first);
-  else
-    hipLaunchKernelGGL((k_att_contig<1, kAttNT>), dim3(std::min<unsigned>(agrid, (unsigned)n_first)), dim3(kAttNT), 0, s,
-                       sa, nullptr, nullptr, nullptr, level0 ? st->act0.as<int32_t>() : nullptr, n_first);
-  ST_TRY(hipGetLastError());
-  t_span(st, WF_PHASE_ATTACH, t_attach, t_mark(st, s));
 
-  // explain_one by one wave per contig (k_one); the dense workgroup (k_decide<3>) gets the
-  // contigs it hands over and the ones it leaves open (explain_two)
-  sa.one_list = st->one_list.as<int32_t>();
-  // roll-up levels
-  Buf* act[2] = {&st->act0, &st->act1};
-  Buf* base[2] = {&st->base0, &st->base1};
-  const unsigned leaf_grid = (unsigned)st->cus * 8u;   // k_leaf: persistent, 8 blocks per CU
-  // Level counters: level L counts into block L of lvl_ctr; the host reads them after each
-  // level through the mailbox
-  const int n_lv = kMaxIter + 2;
-  ST_TRY(st->lvl_ctr.ensure(s, (size_t)n_lv * 8 * sizeof(unsigned long long)));
-  ST_TRY(hipMemsetAsync(st->lvl_ctr.p, 0, (size_t)n_lv * 8 * sizeof(unsigned long long), s));
-  unsigned long long* lvl_ctr = st->lvl_ctr.as<unsigned long long>();
-  sa.in_counts = nullptr;
-  int n_act = n_l0;
-  int64_t n_keys = keys_l0;
-  int start = 0;
-  if (n_seed > 0) {                     // level 1 begins with the seeds (level 0 appends)
-    hipLaunchKernelGGL(k_set_word, dim3(1), dim3(64), 0, s, lvl_ctr,
-                       ((unsigned long long)n_seed << 40) | (unsigned long long)keys_seed);
-    hipLaunchKernelGGL(k_rekey_seeds, dim3(std::min(n_seed, st->cus * 8)), dim3(256), 0, s, st->act1.as<int32_t>(),
-                       n_seed, sa.catt_off, sa.att_clade, k.parent);
-    ST_TRY(hipGetLastError());
-    if (n_l0 == 0) {
-      start = 1;
-      n_act = n_seed;
-      n_keys = keys_seed;
-    }
-  }
-  if (det) {
-    det->levels.clear();
-    ST_TRY(st->span_cnt.ensure(s, A1 * 4));
-    ST_TRY(st->spans.ensure(s, A1 * 8));
-  }
-  if (st->dec_lds > 64 * 1024) {
-    // per process, thread-safe initialisation (C++11 statics); every device is a gfx950
-    static const hipError_t attr3 = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decide<3>),
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                        160 * 1024 - 1024);
-    ST_TRY(attr3);
-  }
-  for (int level = start; n_act > 0 && level <= kMaxIter; ++level) {
-    sa.counters = lvl_ctr + 8 * level;
-    const int cur = level & 1;
-    sa.act = level == 0 ? (level0 ? st->act_l0.as<int32_t>() : nullptr) : act[cur]->as<int32_t>();
-    sa.act_base = level == 0 && !level0 ? nullptr : base[cur]->as<int64_t>();
-    sa.act_next = act[cur ^ 1]->as<int32_t>();
-    sa.act_base_next = base[cur ^ 1]->as<int64_t>();
-    const int cb = bits_for(n_act);
-    const int end_bit = cb + sa.key_tb + sa.key_lb;
-    if (end_bit > 64) { *err = "sort key wider than 64 bits"; return -1; }
-    hipcub::DoubleBuffer<uint64_t> kbuf(st->keys0.as<uint64_t>(), st->keys1.as<uint64_t>());
-    hipcub::DoubleBuffer<int32_t> vbuf(st->vals0.as<int32_t>(), st->vals1.as<int32_t>());
-    sa.keys = nullptr;
-    sa.vals = nullptr;
-    const int t_seg = t_mark(st, s);
-    if (n_keys > 0 && sa.sort_cap > kSortMax && !det) {
-      // the stress contigs' whole front end in one launch (k_front_radix), then the rare
-      // wave / leaf segments it listed
-      static const hipError_t fattr = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_front_radix<false>),
-                                                          hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                          (int)radix_lds(kRadixMax));
-      static const hipError_t pattr = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_front_radix<true>),
-                                                          hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                          (int)radix_lds(kRadixMax, true));
-      ST_TRY(fattr);
-      ST_TRY(pattr);
-      const bool packed = sa.key_lb <= 6 && n_tax <= kPackTaxMax;
-      const size_t fr_bytes = ((size_t)n_act + 4) * sizeof(unsigned long long);
-      ST_TRY(st->front.ensure(s, fr_bytes));
-      ST_TRY(hipMemsetAsync(st->front.p, 0, fr_bytes, s));
-      unsigned long long* fr = st->front.as<unsigned long long>();
-      const size_t lds = radix_lds(sa.sort_cap, packed);
-      const int per_cu = std::max(1, (int)((160 * 1024) / (lds + 1024)));   // (+ its static LDS)
-      if (packed)
-        hipLaunchKernelGGL(k_front_radix<true>, dim3(std::min(n_act, st->cus * per_cu)), dim3(kRadixNT), lds, s, sa,
-                           n_act, n_keys, n_tax, fr);
-      else
-        hipLaunchKernelGGL(k_front_radix<false>, dim3(std::min(n_act, st->cus * per_cu)), dim3(kRadixNT), lds, s, sa,
-                           n_act, n_keys, n_tax, fr);
-      hipLaunchKernelGGL(k_front_fin, dim3(1), dim3(64), 0, s, sa, n_act, fr);
-      hipLaunchKernelGGL(k_seg_wave, dim3(st->cus * 32), dim3(64), 0, s, sa);
-      hipLaunchKernelGGL(k_leaf, dim3(leaf_grid), dim3(256), 0, s, sa, n_keys);
-      hipLaunchKernelGGL(k_seg_combine, dim3(st->cus * 4), dim3(256), 0, s, sa, n_keys);
-      ST_TRY(hipGetLastError());
-      sa.keys = kbuf.Current();
-      sa.vals = vbuf.Current();
-    } else if (n_keys > 0) {
-      size_t need = st->tmp.n;
-      if (sa.sort_cap > kSortMax) {
-        static const hipError_t rattr = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sort_radix),
-                                                            hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                            (int)radix_lds(kRadixMax));
-        ST_TRY(rattr);
-        const size_t lds = radix_lds(sa.sort_cap);
-        const int per_cu = std::max(1, (int)((160 * 1024) / lds));
-        hipLaunchKernelGGL(k_sort_radix, dim3(std::min(n_act, st->cus * per_cu)), dim3(kRadixNT), lds, s, sa, n_act,
-                           level, kbuf.Current(), vbuf.Current());
-      } else if (sa.sort_cap > 0) {
-        const size_t lds = (size_t)sa.sort_cap * 8;
-        const int per_cu = std::min(32, std::max(1, (int)((160 * 1024) / lds)));
-        // level 0: one wave per contig (10^4+ contigs fill the chip); later levels have
-        // few contigs, so four waves shorten each contig's sort
-        if (level == 0)
-          hipLaunchKernelGGL(k_sort_contig<64>, dim3(std::min(n_act, st->cus * per_cu)), dim3(64), lds, s,
-                             sa, n_act, level, kbuf.Current(), vbuf.Current());
-        else
-          hipLaunchKernelGGL(k_sort_contig<256>, dim3(std::min(n_act, st->cus * per_cu)), dim3(256), lds,
-                             s, sa, n_act, level, kbuf.Current(), vbuf.Current());
-      } else {
-        hipLaunchKernelGGL(k_keys_active, dim3(std::min(n_act, st->cus * 8)), dim3(256), 0, s, sa,
-                           n_act, kbuf.Current(), vbuf.Current());
-        ST_TRY(hipGetLastError());
-        ST_TRY(hipcub::DeviceRadixSort::SortPairs(st->tmp.p, need, kbuf, vbuf, (int)n_keys, 0, end_bit, s));
-      }
-      ST_TRY(hipGetLastError());
-      sa.keys = kbuf.Current();
-      sa.vals = vbuf.Current();
-      if (sa.sort_cap > 0) {
-        need = st->tmp.n;
-        if (n_act < 32 * kScanNT)        // <= 32 items a thread: one workgroup
-          hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(kScanNT), 0, s, sa.seg_cnt, sa.crank_first, n_act + 1);
-        else
-          ST_TRY(hipcub::DeviceScan::ExclusiveSum(st->tmp.p, need, sa.seg_cnt, sa.crank_first, n_act + 1, s));
-        if (sa.sort_cap > kSortMax)                   // (the radix-sorted stress contigs)
-          hipLaunchKernelGGL(k_seg_build_wide, dim3(std::min(n_act, st->cus * 4)), dim3(kRadixNT), 0, s, sa, n_act,
-                             level, n_keys);
-        else
-          hipLaunchKernelGGL(k_seg_build, dim3(std::min(n_act, st->cus * 32)), dim3(64), 0, s, sa, n_act,
-                             level, n_keys);
-      } else {
-        hipLaunchKernelGGL(k_seg_flags, dim3(grid_for(n_keys)), dim3(256), 0, s, sa, n_keys);
-        need = st->tmp.n;
-        ST_TRY(hipcub::DeviceScan::InclusiveSum(st->tmp.p, need, sa.flags, sa.seg_id, (int)n_keys, s));
-        hipLaunchKernelGGL(k_segs, dim3(grid_for(n_keys)), dim3(256), 0, s, sa, n_keys);
-        hipLaunchKernelGGL(k_gather, dim3(grid_for(n_keys)), dim3(256), 0, s, sa, n_keys);
-        hipLaunchKernelGGL(k_crank_first, dim3(grid_for(n_keys + 1)), dim3(256), 0, s, sa, n_keys, n_act);
-      }
-      if (det)
-        hipLaunchKernelGGL(k_seg_spans, dim3(grid_for(n_keys)), dim3(256), 0, s, sa, n_keys,
-                           st->span_cnt.as<int32_t>(), st->spans.as<int32_t>());
-      // short segments' means by one thread each; one wave per multi-attachment segment, a
-      // serial envelope sweep (62 VGPRs, 2.8 KB LDS -> 32 waves per CU; roll-up levels have
-      // ~10^5 such segments); the rest through the leaf kernels
-      hipLaunchKernelGGL(k_seg_rec, dim3(grid_for(n_keys + 1)), dim3(256), 0, s, sa, n_keys);
-      hipLaunchKernelGGL(k_seg_wave, dim3(st->cus * 32), dim3(64), 0, s, sa);
-      need = st->tmp.n;
-      ST_TRY(hipcub::DeviceScan::ExclusiveSum(st->tmp.p, need, sa.seg_nleaf, sa.leaf_off,
-                                              (int)n_keys + 1, s));
-      hipLaunchKernelGGL(k_leaf_expand, dim3(grid_for(n_keys)), dim3(256), 0, s, sa, n_keys);
-      hipLaunchKernelGGL(k_leaf, dim3(leaf_grid), dim3(256), 0, s, sa, n_keys);
-      hipLaunchKernelGGL(k_seg_combine, dim3(st->cus * 4), dim3(256), 0, s, sa, n_keys);
-      ST_TRY(hipGetLastError());
-    } else {
-      sa.keys = kbuf.Current();
-      sa.vals = vbuf.Current();
-    }
-    t_span(st, WF_PHASE_SEGMENTS, t_seg, t_mark(st, s));
-    if (det) ST_TRY(details_level(st, sa, level, n_act, n_keys, s, det));
-    const int t_dec = t_mark(st, s);
-    const unsigned dgrid = (unsigned)std::min<int64_t>(n_act, (int64_t)st->cus * 16);
-    hipLaunchKernelGGL(k_one, dim3(std::min<int64_t>(n_act, (int64_t)st->cus * 32)), dim3(64), 0, s, sa,
-                       n_act, level, n_keys);
-    // the dense decision for what k_one handed over whole (> 63 loci, more segments than it
-    // holds, --weak-loci assign-unknown) and the > 63-loci contigs it left open (counts on
-    // the device: a grid of rank-independent size, idle blocks exit at once): as many
-    // one-wave workgroups as the arena and 3 waves/SIMD (VGPRs) allow
-    const unsigned dec_per_cu =
-        (unsigned)std::max<int64_t>(1, std::min<int64_t>(12, (160 * 1024) / std::max<int64_t>(st->dec_lds, 1)));
-    hipLaunchKernelGGL(k_decide<3>, dim3(std::min<unsigned>(dgrid, (unsigned)st->cus * dec_per_cu)),
-                       dim3(kDecNT), (size_t)st->dec_lds, s, sa, n_act, level, n_keys);
-    ST_TRY(hipGetLastError());
-    t_span(st, WF_PHASE_DECIDE, t_dec, t_mark(st, s));
-    if (mailbox) {
-      ST_TRY(publish_sync(st, s, sa.counters, 5, nullptr, 0, st->host_counters));
-    } else {
-      ST_TRY(hipMemcpyAsync(st->host_counters, sa.counters, 5 * sizeof(unsigned long long),
-                            hipMemcpyDeviceToHost, s));
-      ST_TRY(spin_sync(s, st->lvl_ev[0]));
-    }
-    if (st->host_counters[4]) {                      // (k_front_radix's look-back never completed)
-      *err = "segment look-back timed out";
-      return -2;
-    }
-    const int n_big = (int)st->host_counters[2];
-    int n_dense = 0;                    // contigs that need the dense decision in an HBM slot
-    const int t_big = n_big > 0 ? t_mark(st, s) : -1;
-    if (n_big > 0 && st->sparse_big) {
-      // the decision from the segment table, one wave per contig (wf_sparse.h): as many
-      // waves as are resident at once (LDS-bound)
-      const int grid = std::min(n_big, st->cus * sparse_waves(st));
-      ST_TRY(st->sp_ws.ensure(s, (size_t)grid * kSpSlot));
-      sa.sp_ws = st->sp_ws.as<char>();
-      hipLaunchKernelGGL(k_big_sparse, dim3(grid), dim3(64), 0, s, sa, level, n_keys);
-      ST_TRY(hipGetLastError());
-      if (mailbox) {
-        ST_TRY(publish_sync(st, s, sa.counters, 4, nullptr, 0, st->host_counters));
-      } else {
-        ST_TRY(hipMemcpyAsync(st->host_counters, sa.counters, 4 * sizeof(unsigned long long),
-                              hipMemcpyDeviceToHost, s));
-        ST_TRY(spin_sync(s, st->lvl_ev[0]));
-      }
-      n_dense = (int)st->host_counters[1];
-    } else {
-      n_dense = n_big;
-    }
-    if (n_dense > 0) {
-      const int64_t slot = ((int64_t)st->host_counters[3] + 255) & ~int64_t(255);
-      // HBM-slot workgroups: as many as are resident at once (135 VGPRs: 3 four-wave
-      // workgroups per CU); cfg5 (30 k stress contigs, round 2) measured 234.7 ms/pass at 2
-      // per CU, 222.8 at 3, 264.5 at 4 (a second, partial round), 230.2 at 8
-      const int slots = std::min(n_dense, st->cus * 3);
-      ST_TRY(st->big_ws.ensure(s, (size_t)slot * slots));
-      sa.k.big_ws = st->big_ws.as<char>();
-      sa.k.slot_bytes = slot;
-      hipLaunchKernelGGL(k_decide_big, dim3(slots), dim3(kBlock), 0, s, sa, level, n_keys,
-                         (n_big > 0 && st->sparse_big) ? 1 : 0);
-      ST_TRY(hipGetLastError());
-      ST_TRY(hipMemcpyAsync(st->host_counters, sa.counters, 4 * sizeof(unsigned long long),
-                            hipMemcpyDeviceToHost, s));
-      ST_TRY(spin_sync(s, st->lvl_ev[0]));
-    }
-    if (n_big > 0) t_span(st, WF_PHASE_BIG, t_big, t_mark(st, s));
-    if (level == start && !st->dec_lds_fixed && n_dense * 50 > n_act && st->dec_lds < 48 * 1024)
-      st->dec_lds += 8 * 1024;   // adaptive arena: grows while > 2% of a first level overflow
-    n_act = (int)(st->host_counters[0] >> 40);
-    n_keys = (int64_t)(st->host_counters[0] & ((1ull << 40) - 1));
-  }
-  return 0;
+  bool done = false;
+  rc = wave_front(C, &done);
+  if (rc || done) return rc;
+  const int t_attach = t_mark(st, s);
+  rc = count_lists(C);
+  if (rc || C.n_first == 0) return rc;              // (0: the wave kernels finished every contig)
+  if ((rc = size_buffers(C)) || (rc = attach(C))) return rc;
+  t_span(st, WF_PHASE_ATTACH, t_attach, t_mark(st, s));
+  return run_levels(C);
 }
 
 __global__ void k_ppot_strip(int64_t* ppot, int n) {
