@@ -384,6 +384,58 @@ typedef struct wf_map_gap_result { /* [n_pairs] each, same residency as the read
 int wf_map_pairs_gapped(wf_ctx* ctx, const wf_map_reads* reads, const wf_map_params* params,
                         const wf_map_gap_params* gap_params, wf_map_result* out, wf_map_gap_result* gap_out);
 
+/* ---- homology search (waafle_search without blastn) --------------------------------------
+ * Ungapped seed-and-extend of database genes (subjects) against the contigs wf_map_index
+ * holds; DESIGN.md §12 states the rule in full.  Not a blastn clone: ungapped HSPs only.
+ * Bases as in the mapper.  Each subject is searched as given (plus) and reverse-complemented
+ * (minus).  Seeds of seed_len bases at subject offsets 0, stride, 2 stride, ...; a seed with
+ * an N, or with more than max_occ occurrences in the index, is unused (the index's own
+ * max_occ is not read).  Every seed hit is extended on its diagonal to both sides, match +1,
+ * mismatch -2, until the running score has dropped more than xdrop below its best, and never
+ * past an end of its contig or subject.  Per (variant, contig, diagonal) identical HSPs count
+ * once and an HSP strictly contained in another is dropped; those with score >= min_score
+ * are reported.  The subjects of a call are one chunk; the result set of a database does not
+ * depend on how it is cut into chunks. */
+typedef struct wf_search_params {
+  int32_t seed_len;           /* S, 12..32, must equal the index's (default 21) */
+  int32_t stride;             /* T, 1..32 (default 8) */
+  int32_t max_occ;            /* 1..1024 (default 64) */
+  int32_t xdrop;              /* X, 1..1000 (default 20) */
+  int32_t min_score;          /* >= 1 (default 28) */
+  int32_t _pad[3];
+} wf_search_params;
+
+typedef struct wf_search_subjects { /* host memory */
+  int64_t n_subjects;         /* < 2^31 */
+  const char* seq;            /* [off[n_subjects]] ASCII bases, concatenated */
+  const int64_t* off;         /* [n_subjects + 1] off[0] = 0; off[n_subjects] <= 2^30, else
+                                 WF_E_TOOBIG */
+} wf_search_subjects;
+
+typedef struct wf_search_result { /* caller-owned host arrays of `capacity` records, 0-based */
+  int64_t capacity;
+  int64_t n;                  /* out: records found (may exceed capacity, see wf_search) */
+  int32_t* contig;            /* contig index */
+  int32_t* subject;           /* subject index within the call */
+  uint8_t* minus;             /* 0: the subject as given, 1: reverse-complemented */
+  int32_t* qstart;            /* first contig base of the HSP */
+  int32_t* sstart;            /* first base of the HSP on the variant (plus: the subject, minus:
+                                 its reverse complement) */
+  int32_t* length;
+  int32_t* matches;
+  int64_t seed_hits;          /* out, diagnostics: seed hits of the call, those skipped because */
+  int64_t seeds_skipped;      /*   their predecessor on the diagonal gives the same HSP, and    */
+  int64_t raw_hsps;           /*   the HSPs extended, before de-duplication                     */
+} wf_search_result;
+
+/* Records sorted by (contig, subject, minus, qstart, sstart, length).  WF_E_STATE before
+   wf_map_index; WF_E_BADINPUT for a parameter out of range or a seed_len other than the
+   index's; WF_E_TOOBIG for more than 2^31 - 1 seed hits in the call.  With more than
+   `capacity` records the first `capacity` are written, n is the full count and the call
+   returns WF_E_NOMEM: repeat it with more room.  Returns after the work is done. */
+int wf_search(wf_ctx* ctx, const wf_search_subjects* subjects, const wf_search_params* params,
+              wf_search_result* out);
+
 /* ---- --write-details (orgscorer.py:766-812, 931-937) --------------------------------
  * With details on, the next wf_score (staged mode) also records, for every roll-up level,
  * the contigs it evaluated and each (contig, clade, locus) segment of that level: its gene

@@ -1,0 +1,131 @@
+"""Throughput of the built-in homology search (wf_map_index / wf_search) on one MI355X.
+
+    python scripts/search_bench.py [--contigs 10000 --contig-length 5000 --db-bases 200000000
+                                    --subject-length 1000 --homolog-share 0.01 --chunk-bases 67108864]
+
+Not bench.py (the flagship workload); the numbers go to DESIGN.md §12 and profiles/search/.
+The workload is seeded: random contigs, and a database of random subjects of which a share
+--homolog-share is cut from the contigs (either strand) with 0..10 % substitutions, that is
+90..100 % identity.  The search parameters are the defaults (S 21, T 8, max_occ 64, X 20,
+min_score 28).  The GPU step runs in a child process under its own time limit
+(--step-timeout); when it fails or runs out of time nothing more is started.
+
+  search  `Searcher.search` on host-resident subjects in chunks of --chunk-bases (copies in
+          and out and the host's de-duplication included), after one warm-up chunk of 2^20
+          bases: wall per chunk, subject bases per second, the seed-hit, extended-HSP and record
+          counts, the share of seed hits skipped by the predecessor shortcut, and the share of
+          the planted homologs with at least one record
+
+Prints one JSON line.  For per-kernel times run the step under
+`rocprofv3 --kernel-trace --stats -- python scripts/search_bench.py --step search ...`.
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if REPO not in sys.path:
+    sys.path.insert(0, REPO)
+
+ASCII = np.frombuffer(b"ACGT", dtype=np.uint8)
+
+
+def parse(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawTextHelpFormatter)
+    ap.add_argument("--contigs", type=int, default=10000)
+    ap.add_argument("--contig-length", type=int, default=5000)
+    ap.add_argument("--db-bases", type=int, default=200000000)
+    ap.add_argument("--subject-length", type=int, default=1000)
+    ap.add_argument("--homolog-share", type=float, default=0.01)
+    ap.add_argument("--chunk-bases", type=int, default=1 << 26, help="subject bases per wf_search call")
+    ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--gpu", type=int, default=0)
+    ap.add_argument("--step", choices=["search"], help="run the step in this process")
+    ap.add_argument("--step-timeout", type=int, default=600, help="seconds for the GPU step")
+    return ap.parse_args(argv)
+
+
+def make_workload(a):
+    """(contig codes, contig offsets, subject codes [n, L], homolog flags)."""
+    rng = np.random.default_rng(a.seed)
+    codes = rng.integers(0, 4, a.contigs * a.contig_length, dtype=np.uint8)
+    off = np.arange(a.contigs + 1, dtype=np.int64) * a.contig_length
+    L = a.subject_length
+    n = a.db_bases // L
+    subj = rng.integers(0, 4, (n, L), dtype=np.uint8)
+    hom = np.flatnonzero(rng.random(n) < a.homolog_share)
+    c = rng.integers(0, a.contigs, len(hom))
+    p = rng.integers(0, a.contig_length - L + 1, len(hom))
+    cut = codes[(off[c] + p)[:, None] + np.arange(L, dtype=np.int64)[None, :]]
+    rate = rng.random(len(hom))[:, None] * 0.10               # 90..100 % identity
+    sub = rng.random(cut.shape) < rate
+    cut = (cut + sub * rng.integers(1, 4, cut.shape, dtype=np.uint8)).astype(np.uint8) & 3
+    minus = rng.random(len(hom)) < 0.5
+    cut[minus] = 3 - cut[minus][:, ::-1]
+    subj[hom] = cut
+    return codes, off, subj, hom
+
+
+def step_search(a):
+    from waafle_amd import search
+    codes, off, subj, hom = make_workload(a)
+    n, L = subj.shape
+    per = max(a.chunk_bases // L, 1)
+    walls, records, found = [], 0, np.zeros(n, bool)
+    with search.Searcher(ASCII[codes], off, device=a.gpu) as s:
+        w = min(n, max((1 << 20) // L, 1))
+        s.search(ASCII[subj[:w]].reshape(-1), np.arange(w + 1, dtype=np.int64) * L)     # warm-up chunk
+        s.stats = dict.fromkeys(s.stats, 0)
+        for lo in range(0, n, per):
+            hi = min(lo + per, n)
+            seq = ASCII[subj[lo:hi]].reshape(-1)
+            soff = np.arange(hi - lo + 1, dtype=np.int64) * L
+            t0 = time.perf_counter()
+            rec = s.search(seq, soff)
+            walls.append(time.perf_counter() - t0)
+            records += len(rec["contig"])
+            found[rec["subject"].astype(np.int64) + lo] = True
+        stats = dict(s.stats)
+    total = sum(walls)
+    return dict(search_s=total, chunk_s=walls, chunk_bases=per * L, subject_bases_per_s=n * L / total,
+                subjects=n, homologs=int(len(hom)), homologs_found_fraction=float(found[hom].mean()) if len(hom) else 0.0,
+                other_subjects_with_records=int(found.sum() - found[hom].sum()), records=records,
+                seed_hits=stats["seed_hits"], seeds_skipped=stats["seeds_skipped"], raw_hsps=stats["raw_hsps"],
+                skipped_share=stats["seeds_skipped"] / max(stats["seed_hits"], 1),
+                timing="host-resident subjects: copies in and out and the host's de-duplication included, "
+                       "one warm-up chunk")
+
+
+def main(argv=None):
+    a = parse(argv)
+    if a.step:
+        print("SEARCH_BENCH_STEP " + json.dumps(step_search(a)))
+        return 0
+    out = dict(workload=dict(contigs=a.contigs, contig_length=a.contig_length, db_bases=a.db_bases,
+                             subject_length=a.subject_length, homolog_share=a.homolog_share,
+                             identity="90..100 %", seed=a.seed,
+                             params=dict(seed_length=21, seed_stride=8, max_seed_hits=64, xdrop=20, min_score=28)))
+    passed = [x for x in (argv if argv is not None else sys.argv[1:])]
+    cmd = [sys.executable, os.path.abspath(__file__), "--step", "search"] + passed
+    try:
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=a.step_timeout, cwd=REPO)
+    except subprocess.TimeoutExpired:
+        print("the search step ran out of time ({} s); stopping".format(a.step_timeout), file=sys.stderr)
+        return 2
+    line = [l for l in r.stdout.splitlines() if l.startswith("SEARCH_BENCH_STEP ")]
+    if r.returncode != 0 or not line:
+        sys.stderr.write(r.stderr[-4000:])
+        print("the search step failed (exit {}); stopping".format(r.returncode), file=sys.stderr)
+        return 1
+    out.update(json.loads(line[-1][len("SEARCH_BENCH_STEP "):]))
+    print(json.dumps(out))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

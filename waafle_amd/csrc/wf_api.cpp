@@ -766,6 +766,48 @@ int wf_map_pairs_gapped(wf_ctx* ctx, const wf_map_reads* rd, const wf_map_params
   return rc ? fail(ctx, rc, "%s", err.c_str()) : WF_OK;
 }
 
+int wf_search(wf_ctx* ctx, const wf_search_subjects* sb, const wf_search_params* p, wf_search_result* r) {
+  if (!ctx) return WF_E_BADINPUT;
+  if (!sb || !p || !r) return fail(ctx, WF_E_BADINPUT, "null subjects/params/result");
+  r->n = 0;
+  r->seed_hits = r->seeds_skipped = r->raw_hsps = 0;
+  if (p->seed_len < 12 || p->seed_len > 32) return fail(ctx, WF_E_BADINPUT, "seed_len %d outside 12..32", p->seed_len);
+  if (p->stride < 1 || p->stride > 32) return fail(ctx, WF_E_BADINPUT, "stride %d outside 1..32", p->stride);
+  if (p->max_occ < 1 || p->max_occ > 1024) return fail(ctx, WF_E_BADINPUT, "max_occ %d outside 1..1024", p->max_occ);
+  if (p->xdrop < 1 || p->xdrop > 1000) return fail(ctx, WF_E_BADINPUT, "xdrop %d outside 1..1000", p->xdrop);
+  if (p->min_score < 1) return fail(ctx, WF_E_BADINPUT, "min_score %d below 1", p->min_score);
+  if (sb->n_subjects < 0 || sb->n_subjects >= ((int64_t)1 << 31))
+    return fail(ctx, WF_E_BADINPUT, "n_subjects outside [0, 2^31)");
+  if (r->capacity < 0) return fail(ctx, WF_E_BADINPUT, "negative capacity");
+  int S = 0, occ = 0;
+  if (!wf::map_index_params(ctx->map, &S, &occ)) return fail(ctx, WF_E_STATE, "wf_search before wf_map_index");
+  if (S != p->seed_len) return fail(ctx, WF_E_BADINPUT, "seed_len %d differs from the index's %d", p->seed_len, S);
+  if (sb->n_subjects == 0) return WF_OK;
+  if (!sb->off) return fail(ctx, WF_E_BADINPUT, "null subject offsets");
+  if (sb->off[0] != 0) return fail(ctx, WF_E_BADINPUT, "subject offsets must start at 0");
+  for (int64_t i = 0; i < sb->n_subjects; ++i)
+    if (sb->off[i + 1] < sb->off[i]) return fail(ctx, WF_E_BADINPUT, "subject offsets decrease at subject %lld", (long long)i);
+  const int64_t total = sb->off[sb->n_subjects];
+  if (total > ((int64_t)1 << 30)) return fail(ctx, WF_E_TOOBIG, "a chunk of %lld bases (at most 2^30)", (long long)total);
+  if (total > 0 && !sb->seq) return fail(ctx, WF_E_BADINPUT, "null subject bases");
+  if (r->capacity > 0 && (!r->contig || !r->subject || !r->minus || !r->qstart || !r->sstart || !r->length ||
+                          !r->matches))
+    return fail(ctx, WF_E_BADINPUT, "null result arrays");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const wf::SearchRule rule{p->stride, p->max_occ, p->xdrop, p->min_score};
+  const wf::SearchOut out{r->capacity, r->contig, r->subject, r->minus, r->qstart, r->sstart, r->length, r->matches};
+  wf::SearchStats stats{0, 0, 0};
+  std::string err;
+  const int rc = wf::search_run(ctx->map, sb->seq, sb->off, sb->n_subjects, rule, out, &r->n, &stats, ctx->stream, &err);
+  if (rc) return fail(ctx, rc, "%s", err.c_str());
+  r->seed_hits = stats.seed_hits;
+  r->seeds_skipped = stats.skipped;
+  r->raw_hsps = stats.raw_hsps;
+  if (r->n > r->capacity)
+    return fail(ctx, WF_E_NOMEM, "%lld records, room for %lld", (long long)r->n, (long long)r->capacity);
+  return WF_OK;
+}
+
 int wf_details_enable(wf_ctx* ctx, int on) {
   if (!ctx) return WF_E_BADINPUT;
   ctx->details_on = on != 0;

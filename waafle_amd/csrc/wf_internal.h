@@ -192,6 +192,20 @@ struct MapGapOut { int8_t* d1; int8_t* d2; int16_t* k1; int16_t* k2; uint8_t* fl
 int map_pairs_gapped(MapState* st, const MapReads& rd, const MapRule& rule, int max_gap, const MapOut& out,
                      const MapGapOut& gout, hipStream_t s, std::string* err);
 
+// homology search (wf_search.hip): ungapped seed-and-extend of one chunk of subjects against
+// the mapper's index.  The records come back sorted by (contig, subject,
+// minus, qstart, sstart, length); at most `capacity` are written, *n is the full count.
+// 0, or -2 / -7 with the message in *err.
+struct SearchRule { int stride, max_occ, xdrop, min_score; };
+struct SearchOut {
+  int64_t capacity;
+  int32_t* contig; int32_t* subject; uint8_t* minus; int32_t* qstart; int32_t* sstart; int32_t* length;
+  int32_t* matches;
+};
+struct SearchStats { int64_t seed_hits, skipped, raw_hsps; };
+int search_run(MapState* st, const char* seq, const int64_t* off, int64_t n_subjects, const SearchRule& rule,
+               const SearchOut& out, int64_t* n, SearchStats* stats, hipStream_t s, std::string* err);
+
 // --write-details: per roll-up level, the evaluated (active) contigs and the segment
 // records of the level, copied to the host (wf_staged.hip details_level)
 struct DetailsLevel {

@@ -126,6 +126,21 @@ class WfMapGapResult(C.Structure):
     _fields_ = [("d1", _P), ("d2", _P), ("k1", _P), ("k2", _P), ("flags", _P)]
 
 
+class WfSearchParams(C.Structure):
+    _fields_ = [("seed_len", C.c_int32), ("stride", C.c_int32), ("max_occ", C.c_int32),
+                ("xdrop", C.c_int32), ("min_score", C.c_int32), ("_pad", C.c_int32 * 3)]
+
+
+class WfSearchSubjects(C.Structure):
+    _fields_ = [("n_subjects", C.c_int64), ("seq", _P), ("off", _P)]
+
+
+class WfSearchResult(C.Structure):
+    _fields_ = [("capacity", C.c_int64), ("n", C.c_int64), ("contig", _P), ("subject", _P),
+                ("minus", _P), ("qstart", _P), ("sstart", _P), ("length", _P), ("matches", _P),
+                ("seed_hits", C.c_int64), ("seeds_skipped", C.c_int64), ("raw_hsps", C.c_int64)]
+
+
 class WfDetails(C.Structure):
     _fields_ = [("n_evals", C.c_int64), ("eval_contig", _P), ("eval_level", _P),
                 ("n_segs", C.c_int64), ("seg_level", _P), ("seg_contig", _P), ("seg_clade", _P),
@@ -161,6 +176,8 @@ SIGNATURES = {
     "wf_map_pairs_gapped": (C.c_int, [C.c_void_p, C.POINTER(WfMapReads), C.POINTER(WfMapParams),
                                       C.POINTER(WfMapGapParams), C.POINTER(WfMapResult),
                                       C.POINTER(WfMapGapResult)]),
+    "wf_search": (C.c_int, [C.c_void_p, C.POINTER(WfSearchSubjects), C.POINTER(WfSearchParams),
+                            C.POINTER(WfSearchResult)]),
     "wf_details_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "wf_details_read": (C.c_int, [C.c_void_p, C.POINTER(WfDetails)]),
 }

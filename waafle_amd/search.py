@@ -1,0 +1,329 @@
+"""`waafle_search` drop-in CLI (waafle_search.py), with a built-in GPU search in place of blastn.
+
+    python -m waafle_amd.search contigs.fna waafledb [--out --threads --blastn]
+    python -m waafle_amd.search contigs.fna genes.fna --searcher native [--seed-length 21 ...]
+
+`--searcher blastn` (the default) issues exactly the reference's blastn command.  `--searcher
+native` runs the ungapped seed-and-extend search of wf_search.hip on one MI355X (DESIGN.md §12
+states the rule): the contigs are indexed once (wf_map_index), the database genes stream
+through in chunks as subjects (wf_search), and the table is written in the reference's 15
+columns.  It is not a blastn clone: ungapped HSPs only, so a diverged homolog with indels
+comes out as several HSPs with lower subject coverage than blastn would report.
+
+Host side (this module): the streaming subject-FASTA reader, the calls into wf_search, the
+ordering and --max-target-seqs step and the row writer.
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import gzip
+import math
+import os
+import sys
+
+import numpy as np
+
+from . import inputs, lib as L, mapper
+
+DEFAULTS = dict(seed_length=21, seed_stride=8, max_seed_hits=64, xdrop=20, min_score=28)
+MAX_TARGET_SEQS = 10000          # utils.c_max_target_seqs
+CHUNK_BASES = 1 << 28
+LAMBDA, K = 1.28, 0.46           # bit score = (LAMBDA * score - ln K) / ln 2
+BLAST_FORMAT = "6 qseqid sseqid qlen slen length qstart qend sstart send pident positive gaps evalue " \
+               "bitscore sstrand"                            # utils.c_blast_format_string
+
+RECORD_FIELDS = (("contig", np.int32), ("subject", np.int32), ("minus", np.uint8), ("qstart", np.int32),
+                 ("sstart", np.int32), ("length", np.int32), ("matches", np.int32))
+STAT_FIELDS = ("seed_hits", "seeds_skipped", "raw_hsps")
+
+
+class SearchError(inputs.InputError):
+    pass
+
+
+# ---------------------------------------------------------------------------
+# device calls
+# ---------------------------------------------------------------------------
+
+class Searcher:
+    """One context with the index of one contig set; `search` runs wf_search on one chunk of
+    subjects and returns its records (RECORD_FIELDS, subject indices within the chunk)."""
+
+    def __init__(self, seq, off, seed_length=21, seed_stride=8, max_seed_hits=64, xdrop=20, min_score=28,
+                 device=0, capacity=1 << 16):
+        self.params = L.WfSearchParams(seed_len=int(seed_length), stride=int(seed_stride),
+                                       max_occ=int(max_seed_hits), xdrop=int(xdrop), min_score=int(min_score))
+        self.capacity = max(int(capacity), 1)
+        self.stats = dict.fromkeys(STAT_FIELDS, 0)
+        # the index's own max_occ belongs to the read mapper and is not read by the search
+        self.mapper = mapper.Mapper(seq, off, seed_length=int(seed_length), device=device)
+        self.so, self.h = self.mapper.so, self.mapper.h
+
+    def index(self, seq, off):
+        self.mapper.index(seq, off)
+
+    def search_once(self, seq, off, capacity, params=None):
+        """(return code, full record count, records written): one wf_search call."""
+        seq = np.ascontiguousarray(seq, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        out = {f: np.zeros(capacity, dt) for f, dt in RECORD_FIELDS}
+        sb = L.WfSearchSubjects(n_subjects=len(off) - 1, seq=L.ptr(seq), off=L.ptr(off))
+        r = L.WfSearchResult(capacity=capacity, **{f: L.ptr(out[f]) for f, _ in RECORD_FIELDS})
+        rc = self.so.wf_search(self.mapper.h, C.byref(sb), C.byref(params or self.params), C.byref(r))
+        if rc == L.WF_OK:
+            for f in STAT_FIELDS:
+                self.stats[f] += getattr(r, f)
+        n = int(r.n)
+        return rc, n, {f: a[:min(n, capacity)] for f, a in out.items()}
+
+    def search(self, seq, off, params=None):
+        rc, n, out = self.search_once(seq, off, self.capacity, params)
+        if rc == L.WF_E_NOMEM:                              # the call is repeatable with more room
+            self.capacity = max(n, 2 * self.capacity)
+            rc, n, out = self.search_once(seq, off, self.capacity, params)
+        if rc != L.WF_OK:
+            raise L.WaafleHipError(rc, self.so.wf_last_error(self.mapper.h).decode())
+        return out
+
+    def close(self):
+        self.mapper.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def search_chunk(searcher, seq, off):
+    """`Searcher.search`; a chunk that is refused as too big (WF_E_TOOBIG) is halved, down to
+    one subject."""
+    try:
+        return searcher.search(seq, off)
+    except L.WaafleHipError as exc:
+        n = len(off) - 1
+        if exc.code != L.WF_E_TOOBIG:
+            raise
+        if n <= 1:
+            raise SearchError("a single subject is too big to search: {}".format(exc.msg))
+    h = n // 2
+    a = search_chunk(searcher, seq[:off[h]], off[:h + 1])
+    b = search_chunk(searcher, seq[off[h]:], off[h:] - off[h])
+    b["subject"] = b["subject"] + np.int32(h)
+    return {f: np.concatenate([a[f], b[f]]) for f in a}
+
+
+# ---------------------------------------------------------------------------
+# the subject FASTA
+# ---------------------------------------------------------------------------
+
+def _open(path):
+    return gzip.open(path, "rb") if str(path).endswith(".gz") else open(path, "rb")
+
+
+def iter_subject_chunks(path, chunk_bases=CHUNK_BASES):
+    """(ids, seq, off) per chunk, in file order: whole subjects, at most `chunk_bases` bases
+    together (a longer subject is a chunk of its own).  ids: the header up to the first
+    whitespace, which must be a WAAFLE header (id|taxon|system=name...)."""
+    ids, parts, sizes, held = [], [], [], 0
+
+    def flush(n):
+        """the first n subjects held"""
+        nonlocal ids, parts, sizes, held
+        off = np.zeros(n + 1, np.int64)
+        np.cumsum(sizes[:n], out=off[1:])
+        seq = np.frombuffer(b"".join(b"".join(p) for p in parts[:n]), dtype=np.uint8)
+        out = (ids[:n], seq, off)
+        ids, parts, sizes = ids[n:], parts[n:], sizes[n:]
+        held = sum(sizes)
+        return out
+
+    with _open(path) as fh:
+        for line in fh:
+            line = line.strip()
+            if not line:
+                continue
+            if line[:1] == b">":
+                if len(ids) > 1 and held > chunk_bases:      # the last one complete does not fit
+                    yield flush(len(ids) - 1)
+                if len(ids) == 1 and held >= chunk_bases:
+                    yield flush(1)
+                words = line[1:].split()
+                sid = words[0].decode() if words else ""
+                if "|" not in sid:
+                    raise SearchError("bad subject id header: {} (a WAAFLE header is id|taxon|...)".format(sid))
+                ids.append(sid)
+                parts.append([])
+                sizes.append(0)
+            else:
+                if not ids:
+                    raise SearchError("sequence before the first FASTA header in {}".format(path))
+                parts[-1].append(line)
+                sizes[-1] += len(line)
+                held += len(line)
+    if len(ids) > 1 and held > chunk_bases:
+        yield flush(len(ids) - 1)
+    if ids:
+        yield flush(len(ids))
+
+
+# ---------------------------------------------------------------------------
+# ordering and rows
+# ---------------------------------------------------------------------------
+
+def score_of(rec):
+    return 3 * rec["matches"].astype(np.int64) - 2 * rec["length"].astype(np.int64)
+
+
+def order_records(rec, max_target_seqs=MAX_TARGET_SEQS):
+    """Indices of the records to write, in the table's order: by contig; within a contig the
+    subjects are ranked by (-best score, subject) and those past `max_target_seqs` lose their
+    rows; the rest go by (-score, subject, minus, qstart, sstart)."""
+    n = len(rec["contig"])
+    if n == 0:
+        return np.zeros(0, np.int64)
+    score = score_of(rec)
+    contig, subject = rec["contig"].astype(np.int64), rec["subject"].astype(np.int64)
+    pair, inv = np.unique((contig << 32) | subject, return_inverse=True)
+    best = np.full(len(pair), np.iinfo(np.int64).min)
+    np.maximum.at(best, inv, score)
+    pc, ps = pair >> 32, pair & 0xFFFFFFFF
+    o = np.lexsort((ps, -best, pc))
+    first = np.flatnonzero(np.concatenate([[True], pc[o][1:] != pc[o][:-1]]))
+    run = np.repeat(first, np.diff(np.concatenate([first, [len(o)]])))
+    keep_pair = np.zeros(len(pair), bool)
+    keep_pair[o] = (np.arange(len(o)) - run) < max_target_seqs
+    idx = np.flatnonzero(keep_pair[inv])
+    o2 = np.lexsort((rec["sstart"][idx], rec["qstart"][idx], rec["minus"][idx], subject[idx], -score[idx],
+                     contig[idx]))
+    return idx[o2]
+
+
+def bitscore_text(score):
+    bits = (LAMBDA * score - math.log(K)) / math.log(2)
+    return str(int(bits)) if bits > 99.9 else "%.1f" % bits
+
+
+def format_rows(rec, order, contig_names, contig_lens, subject_ids, subject_lens, db_bases):
+    """The 15 columns of utils.c_blast_fields, tab-separated, 1-based; a minus HSP has
+    descending subject coordinates.  evalue = K qlen D exp(-LAMBDA score), D the database's
+    bases: no length adjustment, not BLAST's effective-length value."""
+    out = []
+    cols = [rec[f][order].tolist() for f, _ in RECORD_FIELDS]
+    for c, g, minus, qs, ss, length, m in zip(*cols):
+        score, M, qlen = 3 * m - 2 * length, int(subject_lens[g]), int(contig_lens[c])
+        s0, s1 = (M - ss, M - ss - length + 1) if minus else (ss + 1, ss + length)
+        ev = K * qlen * db_bases * math.exp(-LAMBDA * score)
+        out.append("\t".join(str(v) for v in (
+            contig_names[c], subject_ids[g], qlen, M, length, qs + 1, qs + length, s0, s1,
+            "%.3f" % (100.0 * m / length), m, 0, "%.2e" % ev, bitscore_text(score),
+            "minus" if minus else "plus")))
+    return out
+
+
+def search_files(query, db, out_path, device=0, chunk_bases=CHUNK_BASES, max_target_seqs=MAX_TARGET_SEQS,
+                 say=lambda *a: None, **params):
+    """The native search of the FASTA `db` against the contigs `query`, written to `out_path`.
+    Returns the searcher's counters plus rows, subjects and database bases."""
+    names, seq, off = mapper.read_fasta(query)
+    ids, lens, parts = [], [], []
+    with Searcher(seq, off, device=device, **params) as s:
+        for cid, cseq, coff in iter_subject_chunks(db, chunk_bases):
+            rec = search_chunk(s, cseq, coff)
+            rec["subject"] = rec["subject"] + np.int32(len(ids))
+            parts.append(rec)
+            ids += cid
+            lens.append(np.diff(coff))
+            say("  {:,} subjects searched, {:,} records".format(len(ids), sum(len(p["contig"]) for p in parts)))
+        stats = dict(s.stats)
+    rec = {f: np.concatenate([p[f] for p in parts]) if parts else np.zeros(0, dt) for f, dt in RECORD_FIELDS}
+    lens = np.concatenate(lens) if lens else np.zeros(0, np.int64)
+    order = order_records(rec, max_target_seqs)
+    rows = format_rows(rec, order, names, np.diff(off), ids, lens, int(lens.sum()))
+    with open(out_path, "w") as fh:
+        fh.write("".join(r + "\n" for r in rows))
+    stats.update(rows=len(rows), subjects=len(ids), db_bases=int(lens.sum()))
+    return stats
+
+
+# ---------------------------------------------------------------------------
+# cli
+# ---------------------------------------------------------------------------
+
+def build_parser():
+    ap = argparse.ArgumentParser(
+        description="Step 1 in the WAAFLE pipeline: search a set of contigs against a WAAFLE database,\n"
+                    "with blastn (the reference's command) or with the built-in ungapped GPU search.",
+        formatter_class=argparse.RawTextHelpFormatter)
+    ap.add_argument("query", help="contigs file (fasta format)")
+    ap.add_argument("db", help="path to WAAFLE BLAST database; with --searcher native: the genes' FASTA\n"
+                               "file (plain or .gz) with WAAFLE headers (id|taxon|system=name...).  The\n"
+                               "binary files of a BLAST database cannot be read: get the FASTA with\n"
+                               "`blastdbcmd -db <db> -entry all`")
+    ap.add_argument("--blastn", default="blastn", metavar="<path>", help="path to blastn binary\n[default: $PATH]")
+    ap.add_argument("--threads", default="1", metavar="<int>",
+                    help="number of CPU cores to use in blastn search\n[default: 1]")
+    ap.add_argument("--out", default=None, metavar="<path>",
+                    help="path for blast output file\n[default: <derived from input>]")
+    ap.add_argument("--searcher", choices=["blastn", "native"], default="blastn",
+                    help="blastn: run the reference's blastn command; native: the built-in ungapped\n"
+                         "seed-and-extend search on the GPU (not a blastn clone)\n[default: blastn]")
+    g = ap.add_argument_group("native search (defaults are choices, not measured optima)")
+    g.add_argument("--seed-length", type=int, default=DEFAULTS["seed_length"], metavar="<12..32>")
+    g.add_argument("--seed-stride", type=int, default=DEFAULTS["seed_stride"], metavar="<1..32>")
+    g.add_argument("--max-seed-hits", type=int, default=DEFAULTS["max_seed_hits"], metavar="<1..1024>",
+                   help="a seed with more occurrences in the contigs is unused")
+    g.add_argument("--xdrop", type=int, default=DEFAULTS["xdrop"], metavar="<1..1000>")
+    g.add_argument("--min-score", type=int, default=DEFAULTS["min_score"], metavar="<int>",
+                   help="least raw score (match +1, mismatch -2) reported")
+    g.add_argument("--max-target-seqs", type=int, default=MAX_TARGET_SEQS, metavar="<int>")
+    g.add_argument("--chunk-bases", type=int, default=CHUNK_BASES, metavar="<int>",
+                   help="subject bases per device call")
+    g.add_argument("--gpu", type=int, default=0, metavar="<int>")
+    return ap
+
+
+def default_out(query):
+    """utils.path2name / name2path: ./<file name up to its first dot>.blastout"""
+    return os.path.join(".", os.path.split(query)[1].split(".")[0] + ".blastout")
+
+
+def blastn_command(args):
+    """waafle_search.py:94-112, the same string."""
+    return " ".join(["{BLASTN}", "-query {QUERY}", "-db {DB}", "-out {OUTFILE}", "-max_target_seqs {MAXTAR}",
+                     "-num_threads {THREADS}", "-outfmt '{FORMAT}'"]).format(
+        QUERY=args.query, OUTFILE=args.out, BLASTN=args.blastn, DB=args.db, MAXTAR=MAX_TARGET_SEQS,
+        THREADS=args.threads, FORMAT=BLAST_FORMAT)
+
+
+def die(*args):
+    inputs.say(*(["LETHAL ERROR:"] + list(args)))
+    sys.exit("EXITING.")
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    if args.out is None:
+        args.out = default_out(args.query)
+    if args.searcher == "blastn":
+        command = blastn_command(args)
+        inputs.say("Executing command:", command)
+        os.system(command)
+        inputs.say("Finished successfully.")
+        return
+    if args.max_target_seqs < 1 or args.chunk_bases < 1:
+        die("--max-target-seqs and --chunk-bases must be positive")
+    try:
+        stats = search_files(args.query, args.db, args.out, device=args.gpu, chunk_bases=args.chunk_bases,
+                             max_target_seqs=args.max_target_seqs, say=inputs.say,
+                             seed_length=args.seed_length, seed_stride=args.seed_stride,
+                             max_seed_hits=args.max_seed_hits, xdrop=args.xdrop, min_score=args.min_score)
+    except (inputs.InputError, OSError, L.WaafleHipError) as exc:
+        die(str(exc))
+    inputs.say("Finished successfully ({:,} rows from {:,} subjects; {:,} seed hits).".format(
+        stats["rows"], stats["subjects"], stats["seed_hits"]))
+
+
+if __name__ == "__main__":
+    main()
