@@ -29,7 +29,8 @@ extern "C" {
                                  6: wf_batch.hit_key (packed hit record), wf_pack_hit_keys;
                                     WF_OPT_WAVE_TWO 0 (the round-3 hand-over flow) retired;
                                     still 6 (additive): wf_map_index, wf_map_pairs;
-                                    still 6 (additive): wf_map_pairs_gapped */
+                                    still 6 (additive): wf_map_pairs_gapped;
+                                    still 6 (additive): wf_search, wf_search_gapped */
 
 enum wf_status {
   WF_OK = 0,
@@ -386,7 +387,8 @@ int wf_map_pairs_gapped(wf_ctx* ctx, const wf_map_reads* reads, const wf_map_par
 
 /* ---- homology search (waafle_search without blastn) --------------------------------------
  * Ungapped seed-and-extend of database genes (subjects) against the contigs wf_map_index
- * holds; DESIGN.md §12 states the rule in full.  Not a blastn clone: ungapped HSPs only.
+ * holds; DESIGN.md §12 states the rule in full.  Not a blastn clone: wf_search reports ungapped
+ * HSPs only (wf_search_gapped below extends them by a banded gapped alignment).
  * Bases as in the mapper.  Each subject is searched as given (plus) and reverse-complemented
  * (minus).  Seeds of seed_len bases at subject offsets 0, stride, 2 stride, ...; a seed with
  * an N, or with more than max_occ occurrences in the index, is unused (the index's own
@@ -435,6 +437,51 @@ typedef struct wf_search_result { /* caller-owned host arrays of `capacity` reco
    returns WF_E_NOMEM: repeat it with more room.  Returns after the work is done. */
 int wf_search(wf_ctx* ctx, const wf_search_subjects* subjects, const wf_search_params* params,
               wf_search_result* out);
+
+/* Gapped extension.  wf_search_gapped is wf_search followed by a banded
+ * x-drop alignment from every record: the record's midpoint (variant position i0 = sstart +
+ * length / 2, the contig position on its diagonal) is an anchor, extended to the right and to
+ * the left on its own, over anti-diagonals, within `band` diagonals of the anchor's on each
+ * side, until every cell has dropped more than xdrop_gap below the best so far; never past an
+ * end of its contig or subject.  Scores in half units: match +2, mismatch -4, every gap
+ * column -5 (linear: megablast's +1 / -2 with open 0, extend 2.5).  Per (subject, strand,
+ * contig) identical alignments count once and, in score order, one whose contig and subject
+ * intervals a kept one covers is dropped; those with score2 >= 2 min_score are reported.
+ * score2 = 6 matches - 4 (length - gaps) - 5 gaps.  Not a blastn clone: linear gaps only, no
+ * greedy or affine alignment, no traceback-based trimming; a gap longer than `band` on one
+ * side of the anchor is not bridged, and a homolog with no ungapped record is not found. */
+typedef struct wf_search_gap_params {
+  int32_t band;               /* W, 1..31 (default 15) */
+  int32_t xdrop_gap;          /* Xg, raw score, 1..1000 (default 30) */
+  int32_t _pad[2];
+} wf_search_gap_params;
+
+typedef struct wf_search_gap_result { /* caller-owned host arrays of `capacity` records, 0-based */
+  int64_t capacity;
+  int64_t n;                  /* out: records found (may exceed capacity) */
+  int32_t* contig;
+  int32_t* subject;           /* subject index within the call */
+  uint8_t* minus;
+  int32_t* qstart;            /* contig interval [qstart, qstart + qspan) */
+  int32_t* qspan;
+  int32_t* sstart;            /* variant interval [sstart, sstart + sspan) */
+  int32_t* sspan;
+  int32_t* length;            /* alignment columns: aligned pairs + gaps */
+  int32_t* matches;
+  int32_t* gaps;              /* gap columns */
+  int64_t seed_hits;          /* out, diagnostics: as in wf_search_result, and               */
+  int64_t seeds_skipped;
+  int64_t raw_hsps;
+  int64_t anchors;            /*   the ungapped records extended,                            */
+  int64_t raw_alignments;     /*   the distinct alignments they gave, before the covered go */
+} wf_search_gap_result;
+
+/* Records sorted by (contig, subject, minus, qstart, sstart, qspan, sspan, length, matches,
+   gaps).  Statuses as wf_search, plus WF_E_BADINPUT for band outside 1..31 or xdrop_gap outside
+   1..1000; the same WF_E_NOMEM-and-repeat protocol.  wf_search on the same context is
+   unaffected.  Returns after the work is done. */
+int wf_search_gapped(wf_ctx* ctx, const wf_search_subjects* subjects, const wf_search_params* params,
+                     const wf_search_gap_params* gap_params, wf_search_gap_result* out);
 
 /* ---- --write-details (orgscorer.py:766-812, 931-937) --------------------------------
  * With details on, the next wf_score (staged mode) also records, for every roll-up level,

@@ -1,12 +1,17 @@
-"""Throughput of the built-in homology search (wf_map_index / wf_search) on one MI355X.
+"""Throughput of the built-in homology search (wf_map_index / wf_search / wf_search_gapped) on
+one MI355X.
 
     python scripts/search_bench.py [--contigs 10000 --contig-length 5000 --db-bases 200000000
-                                    --subject-length 1000 --homolog-share 0.01 --chunk-bases 67108864]
+                                    --subject-length 1000 --homolog-share 0.01 --chunk-bases 67108864
+                                    --indel-rate 0.003 --gapped --band 15 --xdrop-gap 30]
 
 Not bench.py (the flagship workload); the numbers go to DESIGN.md §12 and profiles/search/.
 The workload is seeded: random contigs, and a database of random subjects of which a share
 --homolog-share is cut from the contigs (either strand) with 0..10 % substitutions, that is
-90..100 % identity.  The search parameters are the defaults (S 21, T 8, max_occ 64, X 20,
+90..100 % identity; with --indel-rate r every planted homolog also gets Poisson(r x length)
+indels of 1..6 bases, half insertions, half deletions (its length stays --subject-length: it
+is cut longer and trimmed).  --gapped runs `Searcher.search_gapped` in place of
+`Searcher.search`.  The search parameters are the defaults (S 21, T 8, max_occ 64, X 20,
 min_score 28).  The GPU step runs in a child process under its own time limit
 (--step-timeout); when it fails or runs out of time nothing more is started.
 
@@ -14,7 +19,8 @@ min_score 28).  The GPU step runs in a child process under its own time limit
           and out and the host's de-duplication included), after one warm-up chunk of 2^20
           bases: wall per chunk, subject bases per second, the seed-hit, extended-HSP and record
           counts, the share of seed hits skipped by the predecessor shortcut, and the share of
-          the planted homologs with at least one record
+          the planted homologs with at least one record, and with a record that covers at
+          least 0.75 of the subject (the scorer's default --min-scov)
 
 Prints one JSON line.  For per-kernel times run the step under
 `rocprofv3 --kernel-trace --stats -- python scripts/search_bench.py --step search ...`.
@@ -43,6 +49,10 @@ def parse(argv=None):
     ap.add_argument("--subject-length", type=int, default=1000)
     ap.add_argument("--homolog-share", type=float, default=0.01)
     ap.add_argument("--chunk-bases", type=int, default=1 << 26, help="subject bases per wf_search call")
+    ap.add_argument("--indel-rate", type=float, default=0.0, help="indels per base of a planted homolog")
+    ap.add_argument("--gapped", action="store_true", help="wf_search_gapped in place of wf_search")
+    ap.add_argument("--band", type=int, default=15)
+    ap.add_argument("--xdrop-gap", type=int, default=30)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--gpu", type=int, default=0)
     ap.add_argument("--step", choices=["search"], help="run the step in this process")
@@ -65,6 +75,19 @@ def make_workload(a):
     rate = rng.random(len(hom))[:, None] * 0.10               # 90..100 % identity
     sub = rng.random(cut.shape) < rate
     cut = (cut + sub * rng.integers(1, 4, cut.shape, dtype=np.uint8)).astype(np.uint8) & 3
+    if a.indel_rate > 0:                                      # a stream of its own: rate 0 is the old workload
+        rng2 = np.random.default_rng(a.seed + 1)
+        for k in range(len(hom)):
+            p0 = min(int(p[k]), a.contig_length - L - 64)     # room for what the deletions take
+            row = list(cut[k] if p0 == p[k] else codes[off[c[k]] + p0:off[c[k]] + p0 + L])
+            row += list(codes[off[c[k]] + p0 + L:off[c[k]] + p0 + L + 64])
+            for _ in range(min(int(rng2.poisson(a.indel_rate * L)), 10)):
+                at, m = int(rng2.integers(10, L - 10)), int(rng2.integers(1, 7))
+                if rng2.random() < 0.5:
+                    del row[at:at + m]
+                else:
+                    row[at:at] = rng2.integers(0, 4, m).tolist()
+            cut[k] = np.array(row[:L], np.uint8)
     minus = rng.random(len(hom)) < 0.5
     cut[minus] = 3 - cut[minus][:, ::-1]
     subj[hom] = cut
@@ -76,24 +99,29 @@ def step_search(a):
     codes, off, subj, hom = make_workload(a)
     n, L = subj.shape
     per = max(a.chunk_bases // L, 1)
-    walls, records, found = [], 0, np.zeros(n, bool)
-    with search.Searcher(ASCII[codes], off, device=a.gpu) as s:
+    walls, records, found, span = [], 0, np.zeros(n, bool), np.zeros(n, np.int64)
+    gap = dict(band=a.band, xdrop_gap=a.xdrop_gap) if a.gapped else {}
+    with search.Searcher(ASCII[codes], off, device=a.gpu, **gap) as s:
+        run = s.search_gapped if a.gapped else s.search
         w = min(n, max((1 << 20) // L, 1))
-        s.search(ASCII[subj[:w]].reshape(-1), np.arange(w + 1, dtype=np.int64) * L)     # warm-up chunk
+        run(ASCII[subj[:w]].reshape(-1), np.arange(w + 1, dtype=np.int64) * L)          # warm-up chunk
         s.stats = dict.fromkeys(s.stats, 0)
         for lo in range(0, n, per):
             hi = min(lo + per, n)
             seq = ASCII[subj[lo:hi]].reshape(-1)
             soff = np.arange(hi - lo + 1, dtype=np.int64) * L
             t0 = time.perf_counter()
-            rec = s.search(seq, soff)
+            rec = run(seq, soff)
             walls.append(time.perf_counter() - t0)
             records += len(rec["contig"])
             found[rec["subject"].astype(np.int64) + lo] = True
+            np.maximum.at(span, rec["subject"].astype(np.int64) + lo, rec["sspan" if a.gapped else "length"])
         stats = dict(s.stats)
     total = sum(walls)
     return dict(search_s=total, chunk_s=walls, chunk_bases=per * L, subject_bases_per_s=n * L / total,
                 subjects=n, homologs=int(len(hom)), homologs_found_fraction=float(found[hom].mean()) if len(hom) else 0.0,
+                homologs_scov_075=int((span[hom] >= 0.75 * L).sum()), gapped=bool(a.gapped),
+                anchors=stats.get("anchors", 0), raw_alignments=stats.get("raw_alignments", 0),
                 other_subjects_with_records=int(found.sum() - found[hom].sum()), records=records,
                 seed_hits=stats["seed_hits"], seeds_skipped=stats["seeds_skipped"], raw_hsps=stats["raw_hsps"],
                 skipped_share=stats["seeds_skipped"] / max(stats["seed_hits"], 1),
@@ -108,7 +136,8 @@ def main(argv=None):
         return 0
     out = dict(workload=dict(contigs=a.contigs, contig_length=a.contig_length, db_bases=a.db_bases,
                              subject_length=a.subject_length, homolog_share=a.homolog_share,
-                             identity="90..100 %", seed=a.seed,
+                             identity="90..100 %", indel_rate=a.indel_rate, seed=a.seed, gapped=a.gapped,
+                             band=a.band, xdrop_gap=a.xdrop_gap,
                              params=dict(seed_length=21, seed_stride=8, max_seed_hits=64, xdrop=20, min_score=28)))
     passed = [x for x in (argv if argv is not None else sys.argv[1:])]
     cmd = [sys.executable, os.path.abspath(__file__), "--step", "search"] + passed

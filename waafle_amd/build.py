@@ -14,11 +14,12 @@ LIB = os.path.join(HERE, "libwaafle_hip.so")
 SOURCES = [os.path.join(CSRC, "wf_staged.hip"), os.path.join(CSRC, "wf_fast.hip"),
            os.path.join(CSRC, "wf_triage.hip"), os.path.join(CSRC, "wf_genecall.hip"),
            os.path.join(CSRC, "wf_junctions.hip"), os.path.join(CSRC, "wf_map.hip"),
-           os.path.join(CSRC, "wf_search.hip"), os.path.join(CSRC, "wf_api.cpp")]
+           os.path.join(CSRC, "wf_search.hip"), os.path.join(CSRC, "wf_search_gap.hip"),
+           os.path.join(CSRC, "wf_api.cpp")]
 DEPS = SOURCES + [os.path.join(CSRC, "wf_internal.h"), os.path.join(CSRC, "wf_device.h"),
                   os.path.join(CSRC, "wf_sparse.h"), os.path.join(CSRC, "wf_lanes.h"),
                   os.path.join(CSRC, "wf_stamps.h"), os.path.join(CSRC, "wf_attach.h"),
-                  os.path.join(CSRC, "wf_mapstore.h"),
+                  os.path.join(CSRC, "wf_mapstore.h"), os.path.join(CSRC, "wf_searchstate.h"),
                   os.path.join(REPO, "include", "waafle_hip.h")]
 
 # -ffp-contract=off: no a*b+c fusion anywhere, so float64 results match numpy bit-for-bit.

@@ -766,11 +766,10 @@ int wf_map_pairs_gapped(wf_ctx* ctx, const wf_map_reads* rd, const wf_map_params
   return rc ? fail(ctx, rc, "%s", err.c_str()) : WF_OK;
 }
 
-int wf_search(wf_ctx* ctx, const wf_search_subjects* sb, const wf_search_params* p, wf_search_result* r) {
-  if (!ctx) return WF_E_BADINPUT;
-  if (!sb || !p || !r) return fail(ctx, WF_E_BADINPUT, "null subjects/params/result");
-  r->n = 0;
-  r->seed_hits = r->seeds_skipped = r->raw_hsps = 0;
+// the checks wf_search and wf_search_gapped share; *run: there is work to do
+static int check_search_call(wf_ctx* ctx, const wf_search_subjects* sb, const wf_search_params* p, int64_t capacity,
+                             const char* name, bool* run) {
+  *run = false;
   if (p->seed_len < 12 || p->seed_len > 32) return fail(ctx, WF_E_BADINPUT, "seed_len %d outside 12..32", p->seed_len);
   if (p->stride < 1 || p->stride > 32) return fail(ctx, WF_E_BADINPUT, "stride %d outside 1..32", p->stride);
   if (p->max_occ < 1 || p->max_occ > 1024) return fail(ctx, WF_E_BADINPUT, "max_occ %d outside 1..1024", p->max_occ);
@@ -778,9 +777,9 @@ int wf_search(wf_ctx* ctx, const wf_search_subjects* sb, const wf_search_params*
   if (p->min_score < 1) return fail(ctx, WF_E_BADINPUT, "min_score %d below 1", p->min_score);
   if (sb->n_subjects < 0 || sb->n_subjects >= ((int64_t)1 << 31))
     return fail(ctx, WF_E_BADINPUT, "n_subjects outside [0, 2^31)");
-  if (r->capacity < 0) return fail(ctx, WF_E_BADINPUT, "negative capacity");
+  if (capacity < 0) return fail(ctx, WF_E_BADINPUT, "negative capacity");
   int S = 0, occ = 0;
-  if (!wf::map_index_params(ctx->map, &S, &occ)) return fail(ctx, WF_E_STATE, "wf_search before wf_map_index");
+  if (!wf::map_index_params(ctx->map, &S, &occ)) return fail(ctx, WF_E_STATE, "%s before wf_map_index", name);
   if (S != p->seed_len) return fail(ctx, WF_E_BADINPUT, "seed_len %d differs from the index's %d", p->seed_len, S);
   if (sb->n_subjects == 0) return WF_OK;
   if (!sb->off) return fail(ctx, WF_E_BADINPUT, "null subject offsets");
@@ -790,6 +789,18 @@ int wf_search(wf_ctx* ctx, const wf_search_subjects* sb, const wf_search_params*
   const int64_t total = sb->off[sb->n_subjects];
   if (total > ((int64_t)1 << 30)) return fail(ctx, WF_E_TOOBIG, "a chunk of %lld bases (at most 2^30)", (long long)total);
   if (total > 0 && !sb->seq) return fail(ctx, WF_E_BADINPUT, "null subject bases");
+  *run = true;
+  return WF_OK;
+}
+
+int wf_search(wf_ctx* ctx, const wf_search_subjects* sb, const wf_search_params* p, wf_search_result* r) {
+  if (!ctx) return WF_E_BADINPUT;
+  if (!sb || !p || !r) return fail(ctx, WF_E_BADINPUT, "null subjects/params/result");
+  r->n = 0;
+  r->seed_hits = r->seeds_skipped = r->raw_hsps = 0;
+  bool run = false;
+  int rc = check_search_call(ctx, sb, p, r->capacity, "wf_search", &run);
+  if (rc || !run) return rc;
   if (r->capacity > 0 && (!r->contig || !r->subject || !r->minus || !r->qstart || !r->sstart || !r->length ||
                           !r->matches))
     return fail(ctx, WF_E_BADINPUT, "null result arrays");
@@ -798,11 +809,46 @@ int wf_search(wf_ctx* ctx, const wf_search_subjects* sb, const wf_search_params*
   const wf::SearchOut out{r->capacity, r->contig, r->subject, r->minus, r->qstart, r->sstart, r->length, r->matches};
   wf::SearchStats stats{0, 0, 0};
   std::string err;
-  const int rc = wf::search_run(ctx->map, sb->seq, sb->off, sb->n_subjects, rule, out, &r->n, &stats, ctx->stream, &err);
+  rc = wf::search_run(ctx->map, sb->seq, sb->off, sb->n_subjects, rule, out, &r->n, &stats, ctx->stream, &err);
   if (rc) return fail(ctx, rc, "%s", err.c_str());
   r->seed_hits = stats.seed_hits;
   r->seeds_skipped = stats.skipped;
   r->raw_hsps = stats.raw_hsps;
+  if (r->n > r->capacity)
+    return fail(ctx, WF_E_NOMEM, "%lld records, room for %lld", (long long)r->n, (long long)r->capacity);
+  return WF_OK;
+}
+
+int wf_search_gapped(wf_ctx* ctx, const wf_search_subjects* sb, const wf_search_params* p,
+                     const wf_search_gap_params* gp, wf_search_gap_result* r) {
+  if (!ctx) return WF_E_BADINPUT;
+  if (!sb || !p || !gp || !r) return fail(ctx, WF_E_BADINPUT, "null subjects/params/gap params/result");
+  r->n = 0;
+  r->seed_hits = r->seeds_skipped = r->raw_hsps = r->anchors = r->raw_alignments = 0;
+  if (gp->band < 1 || gp->band > 31) return fail(ctx, WF_E_BADINPUT, "band %d outside 1..31", gp->band);
+  if (gp->xdrop_gap < 1 || gp->xdrop_gap > 1000)
+    return fail(ctx, WF_E_BADINPUT, "xdrop_gap %d outside 1..1000", gp->xdrop_gap);
+  bool run = false;
+  int rc = check_search_call(ctx, sb, p, r->capacity, "wf_search_gapped", &run);
+  if (rc || !run) return rc;
+  if (r->capacity > 0 && (!r->contig || !r->subject || !r->minus || !r->qstart || !r->qspan || !r->sstart ||
+                          !r->sspan || !r->length || !r->matches || !r->gaps))
+    return fail(ctx, WF_E_BADINPUT, "null result arrays");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const wf::SearchRule rule{p->stride, p->max_occ, p->xdrop, p->min_score};
+  const wf::SearchGapOut out{r->capacity, r->contig, r->subject, r->minus, r->qstart, r->qspan,
+                             r->sstart,   r->sspan,  r->length,  r->matches, r->gaps};
+  wf::SearchStats stats{0, 0, 0};
+  wf::SearchGapStats gstats{0, 0};
+  std::string err;
+  rc = wf::search_gapped_run(ctx->map, sb->seq, sb->off, sb->n_subjects, rule, gp->band, gp->xdrop_gap, out, &r->n,
+                             &stats, &gstats, ctx->stream, &err);
+  if (rc) return fail(ctx, rc, "%s", err.c_str());
+  r->seed_hits = stats.seed_hits;
+  r->seeds_skipped = stats.skipped;
+  r->raw_hsps = stats.raw_hsps;
+  r->anchors = gstats.anchors;
+  r->raw_alignments = gstats.raw_alignments;
   if (r->n > r->capacity)
     return fail(ctx, WF_E_NOMEM, "%lld records, room for %lld", (long long)r->n, (long long)r->capacity);
   return WF_OK;

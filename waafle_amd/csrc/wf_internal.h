@@ -205,6 +205,18 @@ struct SearchOut {
 struct SearchStats { int64_t seed_hits, skipped, raw_hsps; };
 int search_run(MapState* st, const char* seq, const int64_t* off, int64_t n_subjects, const SearchRule& rule,
                const SearchOut& out, int64_t* n, SearchStats* stats, hipStream_t s, std::string* err);
+// ... with every record extended as an anchor by the banded gapped rule of DESIGN.md §12.5
+// (wf_search_gap.hip).  The records come back sorted by (contig, subject, minus, qstart,
+// sstart, qspan, sspan, length, matches, gaps).  Same return codes.
+struct SearchGapOut {
+  int64_t capacity;
+  int32_t* contig; int32_t* subject; uint8_t* minus; int32_t* qstart; int32_t* qspan; int32_t* sstart;
+  int32_t* sspan; int32_t* length; int32_t* matches; int32_t* gaps;
+};
+struct SearchGapStats { int64_t anchors, raw_alignments; };
+int search_gapped_run(MapState* st, const char* seq, const int64_t* off, int64_t n_subjects, const SearchRule& rule,
+                      int band, int xdrop_gap, const SearchGapOut& out, int64_t* n, SearchStats* stats,
+                      SearchGapStats* gstats, hipStream_t s, std::string* err);
 
 // --write-details: per roll-up level, the evaluated (active) contigs and the segment
 // records of the level, copied to the host (wf_staged.hip details_level)

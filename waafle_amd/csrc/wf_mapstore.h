@@ -1,7 +1,7 @@
 // The contig store and S-mer index of the read mapper (wf_map.hip builds them; wf_search.hip
-// reads them): the device buffers kept in a context, the kernels' view of them, and the
-// device helpers both files use.  Included by those two translation units only; everything
-// here has internal linkage.
+// and wf_search_gap.hip read them): the device buffers kept in a context, the kernels' view of
+// them, and the device helpers those files use.  Included by those three translation units
+// only; everything here has internal linkage.
 #pragma once
 
 #include <string>

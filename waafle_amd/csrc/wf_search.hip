@@ -29,6 +29,7 @@
 
 #include "wf_internal.h"
 #include "wf_mapstore.h"
+#include "wf_searchstate.h"
 
 namespace wf {
 
@@ -40,14 +41,10 @@ struct SearchRaw {            // one extended seed hit
   int32_t score;
 };
 
-struct SearchState {
-  MapBuf seq, off, soff, pk[2], nm[2], cnt, first, start, tmp, raw, ctr;
-};
-
 void search_destroy(SearchState* ss) {
   if (!ss) return;
   MapBuf* bufs[] = {&ss->seq, &ss->off, &ss->soff, &ss->pk[0], &ss->pk[1], &ss->nm[0], &ss->nm[1],
-                    &ss->cnt, &ss->first, &ss->start, &ss->tmp, &ss->raw, &ss->ctr};
+                    &ss->cnt, &ss->first, &ss->start, &ss->tmp, &ss->raw, &ss->ctr, &ss->g_anchor, &ss->g_out};
   for (MapBuf* b : bufs) map_release(*b);
   delete ss;
 }
@@ -355,9 +352,10 @@ int search_device(MapState* st, const char* seq, const int64_t* off, int64_t n, 
 
 }  // namespace
 
-int search_run(MapState* st, const char* seq, const int64_t* off, int64_t n_subjects, const SearchRule& rule,
-               const SearchOut& out, int64_t* n, SearchStats* stats, hipStream_t s, std::string* err) {
-  *n = 0;
+int search_records(MapState* st, const char* seq, const int64_t* off, int64_t n_subjects, const SearchRule& rule,
+                   std::vector<SearchRec>* recs_out, SearchStats* stats, hipStream_t s, std::string* err) {
+  std::vector<SearchRec>& recs = *recs_out;
+  recs.clear();
   *stats = SearchStats{0, 0, 0};
   if (n_subjects == 0 || st->n_kmers == 0) return 0;
   std::vector<SearchRaw> raw;
@@ -373,8 +371,7 @@ int search_run(MapState* st, const char* seq, const int64_t* off, int64_t n_subj
   std::sort(raw.begin(), raw.end(), [](const SearchRaw& x, const SearchRaw& y) {
     return std::make_tuple(x.sm, x.contig, x.delta, x.b, -x.e) < std::make_tuple(y.sm, y.contig, y.delta, y.b, -y.e);
   });
-  struct Rec { int32_t contig, subject, minus, qstart, sstart, length, matches; };
-  std::vector<Rec> recs;
+  using Rec = SearchRec;
   int reach = 0;                                 // the greatest end seen in the group
   for (size_t i = 0; i < raw.size(); ++i) {
     const SearchRaw& x = raw[i];
@@ -391,10 +388,19 @@ int search_run(MapState* st, const char* seq, const int64_t* off, int64_t n_subj
     return std::make_tuple(x.contig, x.subject, x.minus, x.qstart, x.sstart, x.length) <
            std::make_tuple(y.contig, y.subject, y.minus, y.qstart, y.sstart, y.length);
   });
+  return 0;
+}
+
+int search_run(MapState* st, const char* seq, const int64_t* off, int64_t n_subjects, const SearchRule& rule,
+               const SearchOut& out, int64_t* n, SearchStats* stats, hipStream_t s, std::string* err) {
+  *n = 0;
+  std::vector<SearchRec> recs;
+  const int rc = search_records(st, seq, off, n_subjects, rule, &recs, stats, s, err);
+  if (rc) return rc;
   *n = (int64_t)recs.size();
   const int64_t w = std::min<int64_t>(*n, out.capacity);
   for (int64_t i = 0; i < w; ++i) {
-    const Rec& r = recs[(size_t)i];
+    const SearchRec& r = recs[(size_t)i];
     out.contig[i] = r.contig;
     out.subject[i] = r.subject;
     out.minus[i] = (uint8_t)r.minus;

@@ -1,0 +1,298 @@
+// Gapped extension of the homology search on MI355X (gfx950): every ungapped record of a chunk
+// (wf_search.hip) is an anchor, extended to either side by a banded x-drop
+// alignment with linear gap cost.  DESIGN.md §12.5 states the rule; tests/search_gap_oracle.py
+// restates it on the CPU twice.  Scores in half units: match +2, mismatch -4, gap column -5.
+//
+// k_search_gapped: one wavefront per anchor, first the right side, then the left.
+//   lane l <-> band diagonal d = q - p = l - W (2 W + 1 <= 63 lanes), one anti-diagonal
+//   k = p + q per step; the lanes with k - d even hold a cell (p, q) = ((k - d) / 2, (k + d) / 2).
+//   Every lane keeps one (H, g): its cell of step k - 2 when it is active at step k (the
+//   diagonal predecessor), and for its neighbours their cells of step k - 1 (the two gap
+//   predecessors, fetched with __shfl_down / __shfl_up).  best(k) is a wave-wide max of the
+//   step before (wf_lanes.h butterfly, DPP and permlane swaps, no LDS).
+//   Bases: per tile of 64 steps a lane takes 32 consecutive columns of its own diagonal, so it
+//   loads one 32-column mismatch word from the bit planes (the chunk's planes of the anchor's
+//   strand, the index's store) and shifts a bit out of it per active step.  The left side
+//   reads the words below the anchor, bit-reversed.
+//   Loads: a lane loads a word only when one of its 32 columns lies inside the subject and
+//   inside the contig, so the word starts at most 31 positions before such a column: its first
+//   store word is W >= -1 (guarded, reads as N) and its second lies inside the padding.
+// Host (search_gapped_run): the ungapped records are uploaded as anchors, extended in launches
+// of at most kGapLaunch with a synchronisation each, and the reporting step of §12.5 runs in
+// C++: identical alignments once, then per (subject, strand, contig) in score order, those
+// covered by a kept one dropped.
+#include <algorithm>
+#include <climits>
+#include <string>
+#include <tuple>
+#include <vector>
+
+#include "wf_internal.h"
+#include "wf_lanes.h"
+#include "wf_mapstore.h"
+#include "wf_searchstate.h"
+
+namespace wf {
+namespace {
+
+constexpr int kGapLaunch = 1 << 16;             // anchors per k_search_gapped launch
+constexpr int kGapDead = INT_MIN / 2;
+
+struct GapAnchor { int32_t sm, contig, i0, j0; };   // subject << 1 | minus; i0 on the variant, j0 contig-local
+struct GapSide { int32_t H, p, q, g; };
+struct GapRaw { GapSide left, right; };
+
+struct GapArgs {
+  MapIndexView ix;            // the contigs
+  const uint2* vpk[2];        // the chunk: plus store, minus store
+  const uint32_t* vnm[2];
+  const int64_t* off;         // [n_subjects + 1] the subjects' starts in the chunk
+  int64_t total;              // bases of the chunk
+  int W, X2;                  // band half-width; 2 Xg (half units)
+  const GapAnchor* anchor;    // [n]
+  int n;
+  GapRaw* out;                // [n]
+};
+
+// mismatch bits of the 32 columns whose first lies at position vp of the variant store and gp
+// of the contig store; either may be as low as -32 (the bases before a store are N)
+__device__ __forceinline__ uint32_t gap_mis(const GapArgs& A, int strand, int vp, int gp) {
+  const uint2* pk = A.vpk[strand];
+  const uint32_t* nm = A.vnm[strand];
+  const int Wd = vp >> 5, sh = vp & 31;
+  uint2 a = make_uint2(0u, 0u);
+  uint32_t na = ~0u;
+  if (Wd >= 0) {
+    a = pk[Wd];
+    na = nm[Wd];
+  }
+  const uint2 b = pk[Wd + 1];
+  const uint32_t vlo = window32(a.x, b.x, sh), vhi = window32(a.y, b.y, sh), vn = window32(na, nm[Wd + 1], sh);
+  return map_mis_word<true>(A.ix, &vlo, &vhi, &vn, 0, gp);
+}
+
+__device__ __forceinline__ int wave_max(int x) {
+  return wave_butterfly(x, [](int a, int b) { return a > b ? a : b; });
+}
+__device__ __forceinline__ int wave_min(int x) {
+  return wave_butterfly(x, [](int a, int b) { return a < b ? a : b; });
+}
+
+// One side of one anchor, by the whole wave (every lane runs every step; the loop's trip
+// count is wave-uniform).  u: nu bases of the variant, v: nv bases of the contig, walked away
+// from the anchor; vpos, gpos: the store positions of u[0] and v[0].
+template <bool kLeft>
+__device__ __forceinline__ GapSide gap_side(const GapArgs& A, int strand, int vpos, int gpos, int nu, int nv,
+                                            int lane) {
+  const int W = A.W, d = lane - W;
+  const bool inband = lane <= 2 * W;
+  // the columns t (u[t] against v[t + d]) a diagonal move of this lane may read
+  const int tlo = max(0, -d), thi = min(nu, nv - d);
+  int H = lane == W ? 0 : kGapDead, g = 0;       // the lane's latest cell
+  int topH = H, topK = 0, topG = 0;              // the lane's best live cell, the first of equal ones
+  int best = 0;                                  // over the anti-diagonals before k
+  bool prev_live = true;
+  uint32_t mis = ~0u;
+  int t0 = 0;                                    // the column of bit 0 of mis
+  // the last anti-diagonal with a cell in the band; nu < 2^30 (an anchor lies inside its HSP)
+  const int kmax = (int)min((int64_t)nu + nv, 2 * (int64_t)min(nu, nv) + W);
+  for (int k = 1; k <= kmax; ++k) {
+    if (k == 1 || (k & 63) == 0) {               // a tile of steps [k0, k0 + 64), k0 = k & ~63
+      const int k0 = k & ~63;
+      const int kf = k0 + (d & 1);               // the lane's first active step of the tile
+      t0 = ((kf - d) >> 1) - 1;
+      mis = ~0u;
+      if (inband && max(t0, tlo) < min(t0 + 32, thi)) {
+        if (kLeft) mis = __brev(gap_mis(A, strand, vpos - t0 - 31, gpos - d - t0 - 31));
+        else mis = gap_mis(A, strand, vpos + t0, gpos + d + t0);
+      }
+    }
+    const bool active = inband && ((k - d) & 1) == 0;
+    const int p = (k - d) >> 1, q = k - p;
+    int Hu = __shfl_down(H, 1), gu = __shfl_down(g, 1);    // (p - 1, q): diagonal d + 1
+    int Hl = __shfl_up(H, 1), gl = __shfl_up(g, 1);        // (p, q - 1): diagonal d - 1
+    if (lane == 63) Hu = kGapDead;
+    if (lane == 0) Hl = kGapDead;
+    int nh = kGapDead, ng = 0;
+    if (H > kGapDead) {                          // (p - 1, q - 1): column p - 1
+      nh = H + (((mis >> ((p - 1 - t0) & 31)) & 1u) ? -4 : 2);
+      ng = g;
+    }
+    if (Hu > kGapDead && Hu - 5 > nh) { nh = Hu - 5; ng = gu + 1; }
+    if (Hl > kGapDead && Hl - 5 > nh) { nh = Hl - 5; ng = gl + 1; }
+    const bool live = active && p >= 0 && q >= 0 && p <= nu && q <= nv && nh > kGapDead && best - nh <= A.X2;
+    if (active) {
+      H = live ? nh : kGapDead;
+      g = ng;
+    }
+    if (live && nh > topH) { topH = nh; topK = k; topG = ng; }
+    const int m = wave_max(active ? H : kGapDead);
+    if (m == kGapDead) {
+      if (!prev_live) break;
+      prev_live = false;
+    } else {
+      prev_live = true;
+      best = max(best, m);
+    }
+  }
+  // the greatest H; of equal ones the smallest k, then the smallest p
+  const int Hm = wave_max(topH);
+  const int km = wave_min(topH == Hm ? topK : INT_MAX);
+  const int mine = (km - d) >> 1;
+  const int pm = wave_min(topH == Hm && topK == km ? mine : INT_MAX);
+  const int gm = wave_max(topH == Hm && topK == km && mine == pm ? topG : INT_MIN);
+  return GapSide{Hm, pm, km - pm, gm};
+}
+
+__global__ __launch_bounds__(256) void k_search_gapped(const GapArgs A) {
+  const int a = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (a >= A.n) return;                          // the whole wave
+  const int lane = threadIdx.x & 63;
+  const GapAnchor an = A.anchor[a];
+  const int gsub = an.sm >> 1, strand = an.sm & 1;
+  const int64_t o0 = A.off[gsub], o1 = A.off[gsub + 1];
+  const int M = (int)(o1 - o0);
+  const int vbase = (int)(strand ? A.total - o1 : o0);
+  const int c0 = A.ix.coff[an.contig], Lc = A.ix.coff[an.contig + 1] - c0;
+  // bounds before any load; an anchor outside them (never made by the host) extends nowhere
+  const int i0 = min(max(an.i0, 0), M), j0 = min(max(an.j0, 0), Lc);
+  GapRaw out;
+  out.right = gap_side<false>(A, strand, vbase + i0, c0 + j0, M - i0, Lc - j0, lane);
+  out.left = gap_side<true>(A, strand, vbase + i0 - 1, c0 + j0 - 1, i0, j0, lane);
+  if (lane == 0) A.out[a] = out;
+}
+
+#define GAP_TRY(x)                                                                        \
+  do {                                                                                    \
+    hipError_t e_ = (x);                                                                  \
+    if (e_ != hipSuccess) { *err = std::string(#x) + ": " + hipGetErrorString(e_); return -2; } \
+  } while (0)
+#define GAP_RC(x)                    \
+  do {                               \
+    const int rc_ = (x);             \
+    if (rc_) return rc_;             \
+  } while (0)
+
+struct GapAln {
+  int32_t sm, contig, qstart, qspan, sstart, sspan, length, matches, gaps;
+  int64_t score2;
+};
+
+auto aln_key(const GapAln& x) {
+  return std::make_tuple(x.sm, x.contig, -x.score2, x.qstart, x.sstart, x.qspan, x.sspan, x.length, x.matches,
+                         x.gaps);
+}
+
+int gapped_device(MapState* st, const std::vector<GapAnchor>& anchors, int band, int xdrop_gap, int64_t total,
+                  std::vector<GapRaw>* raw, hipStream_t s, std::string* err) {
+  SearchState* ss = st->search;                  // made by search_records: there are anchors
+  GAP_RC(map_ensure(ss->g_anchor, sizeof(GapAnchor) * kGapLaunch, err));
+  GAP_RC(map_ensure(ss->g_out, sizeof(GapRaw) * kGapLaunch, err));
+  GapArgs A{};
+  A.ix = map_view(st);
+  for (int v = 0; v < 2; ++v) {
+    A.vpk[v] = static_cast<const uint2*>(ss->pk[v].p);
+    A.vnm[v] = static_cast<const uint32_t*>(ss->nm[v].p);
+  }
+  A.off = static_cast<const int64_t*>(ss->off.p);
+  A.total = total;
+  A.W = band;
+  A.X2 = 2 * xdrop_gap;
+  A.anchor = static_cast<const GapAnchor*>(ss->g_anchor.p);
+  A.out = static_cast<GapRaw*>(ss->g_out.p);
+  raw->resize(anchors.size());
+  for (size_t a0 = 0; a0 < anchors.size(); a0 += kGapLaunch) {
+    A.n = (int)std::min<size_t>(kGapLaunch, anchors.size() - a0);
+    GAP_TRY(hipMemcpyAsync(ss->g_anchor.p, anchors.data() + a0, sizeof(GapAnchor) * A.n, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_search_gapped, dim3((unsigned)((A.n + 3) / 4)), dim3(256), 0, s, A);
+    GAP_TRY(hipGetLastError());
+    GAP_TRY(hipMemcpyAsync(raw->data() + a0, ss->g_out.p, sizeof(GapRaw) * A.n, hipMemcpyDeviceToHost, s));
+    GAP_TRY(hipStreamSynchronize(s));
+  }
+  return 0;
+}
+
+}  // namespace
+
+int search_gapped_run(MapState* st, const char* seq, const int64_t* off, int64_t n_subjects, const SearchRule& rule,
+                      int band, int xdrop_gap, const SearchGapOut& out, int64_t* n, SearchStats* stats,
+                      SearchGapStats* gstats, hipStream_t s, std::string* err) {
+  *n = 0;
+  *gstats = SearchGapStats{0, 0};
+  std::vector<SearchRec> recs;
+  GAP_RC(search_records(st, seq, off, n_subjects, rule, &recs, stats, s, err));
+  gstats->anchors = (int64_t)recs.size();
+  if (recs.empty()) return 0;
+  std::vector<GapAnchor> anchors(recs.size());
+  for (size_t i = 0; i < recs.size(); ++i) {
+    const SearchRec& r = recs[i];
+    const int32_t i0 = r.sstart + r.length / 2;
+    anchors[i] = GapAnchor{r.subject << 1 | r.minus, r.contig, i0, i0 + (r.qstart - r.sstart)};
+  }
+  std::vector<GapRaw> raw;
+  const int rc = gapped_device(st, anchors, band, xdrop_gap, off[n_subjects], &raw, s, err);
+  if (rc) {
+    (void)hipStreamSynchronize(s);
+    return rc;
+  }
+  std::vector<GapAln> alns(raw.size());
+  for (size_t i = 0; i < raw.size(); ++i) {
+    const GapSide &L = raw[i].left, &R = raw[i].right;
+    GapAln& x = alns[i];
+    x.sm = anchors[i].sm;
+    x.contig = anchors[i].contig;
+    x.qstart = anchors[i].j0 - L.q;
+    x.qspan = L.q + R.q;
+    x.sstart = anchors[i].i0 - L.p;
+    x.sspan = L.p + R.p;
+    x.gaps = L.g + R.g;
+    x.score2 = (int64_t)L.H + R.H;
+    const int64_t pairs = ((int64_t)x.sspan + x.qspan - x.gaps) / 2;
+    x.length = (int32_t)(pairs + x.gaps);
+    x.matches = (int32_t)((x.score2 + 5 * (int64_t)x.gaps + 4 * pairs) / 6);
+  }
+  std::sort(alns.begin(), alns.end(), [](const GapAln& x, const GapAln& y) { return aln_key(x) < aln_key(y); });
+  alns.erase(std::unique(alns.begin(), alns.end(),
+                         [](const GapAln& x, const GapAln& y) { return aln_key(x) == aln_key(y); }),
+             alns.end());
+  gstats->raw_alignments = (int64_t)alns.size();
+  // per (subject, strand, contig), in score order: dropped when a kept one covers both intervals
+  std::vector<GapAln> kept;
+  size_t g0 = 0;                                 // the group's first kept one
+  for (size_t i = 0; i < alns.size(); ++i) {
+    const GapAln& x = alns[i];
+    if (i == 0 || alns[i - 1].sm != x.sm || alns[i - 1].contig != x.contig) g0 = kept.size();
+    bool covered = false;
+    for (size_t k = g0; k < kept.size() && !covered; ++k) {
+      const GapAln& y = kept[k];
+      covered = y.qstart <= x.qstart && x.qstart + x.qspan <= y.qstart + y.qspan && y.sstart <= x.sstart &&
+                x.sstart + x.sspan <= y.sstart + y.sspan;
+    }
+    if (!covered) kept.push_back(x);
+  }
+  kept.erase(std::remove_if(kept.begin(), kept.end(),
+                            [&](const GapAln& x) { return x.score2 < 2 * (int64_t)rule.min_score; }),
+             kept.end());
+  std::sort(kept.begin(), kept.end(), [](const GapAln& x, const GapAln& y) {
+    return std::make_tuple(x.contig, x.sm, x.qstart, x.sstart, x.qspan, x.sspan, x.length, x.matches, x.gaps) <
+           std::make_tuple(y.contig, y.sm, y.qstart, y.sstart, y.qspan, y.sspan, y.length, y.matches, y.gaps);
+  });
+  *n = (int64_t)kept.size();
+  const int64_t w = std::min<int64_t>(*n, out.capacity);
+  for (int64_t i = 0; i < w; ++i) {
+    const GapAln& r = kept[(size_t)i];
+    out.contig[i] = r.contig;
+    out.subject[i] = r.sm >> 1;
+    out.minus[i] = (uint8_t)(r.sm & 1);
+    out.qstart[i] = r.qstart;
+    out.qspan[i] = r.qspan;
+    out.sstart[i] = r.sstart;
+    out.sspan[i] = r.sspan;
+    out.length[i] = r.length;
+    out.matches[i] = r.matches;
+    out.gaps[i] = r.gaps;
+  }
+  return 0;
+}
+
+}  // namespace wf

@@ -141,6 +141,18 @@ class WfSearchResult(C.Structure):
                 ("seed_hits", C.c_int64), ("seeds_skipped", C.c_int64), ("raw_hsps", C.c_int64)]
 
 
+class WfSearchGapParams(C.Structure):
+    _fields_ = [("band", C.c_int32), ("xdrop_gap", C.c_int32), ("_pad", C.c_int32 * 2)]
+
+
+class WfSearchGapResult(C.Structure):
+    _fields_ = [("capacity", C.c_int64), ("n", C.c_int64), ("contig", _P), ("subject", _P),
+                ("minus", _P), ("qstart", _P), ("qspan", _P), ("sstart", _P), ("sspan", _P),
+                ("length", _P), ("matches", _P), ("gaps", _P),
+                ("seed_hits", C.c_int64), ("seeds_skipped", C.c_int64), ("raw_hsps", C.c_int64),
+                ("anchors", C.c_int64), ("raw_alignments", C.c_int64)]
+
+
 class WfDetails(C.Structure):
     _fields_ = [("n_evals", C.c_int64), ("eval_contig", _P), ("eval_level", _P),
                 ("n_segs", C.c_int64), ("seg_level", _P), ("seg_contig", _P), ("seg_clade", _P),
@@ -178,6 +190,8 @@ SIGNATURES = {
                                       C.POINTER(WfMapGapResult)]),
     "wf_search": (C.c_int, [C.c_void_p, C.POINTER(WfSearchSubjects), C.POINTER(WfSearchParams),
                             C.POINTER(WfSearchResult)]),
+    "wf_search_gapped": (C.c_int, [C.c_void_p, C.POINTER(WfSearchSubjects), C.POINTER(WfSearchParams),
+                                   C.POINTER(WfSearchGapParams), C.POINTER(WfSearchGapResult)]),
     "wf_details_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "wf_details_read": (C.c_int, [C.c_void_p, C.POINTER(WfDetails)]),
 }

@@ -2,16 +2,21 @@
 
     python -m waafle_amd.search contigs.fna waafledb [--out --threads --blastn]
     python -m waafle_amd.search contigs.fna genes.fna --searcher native [--seed-length 21 ...]
+    python -m waafle_amd.search contigs.fna genes.fna --searcher native --gapped [--band 15 --xdrop-gap 30]
 
 `--searcher blastn` (the default) issues exactly the reference's blastn command.  `--searcher
-native` runs the ungapped seed-and-extend search of wf_search.hip on one MI355X (DESIGN.md §12
-states the rule): the contigs are indexed once (wf_map_index), the database genes stream
-through in chunks as subjects (wf_search), and the table is written in the reference's 15
-columns.  It is not a blastn clone: ungapped HSPs only, so a diverged homolog with indels
-comes out as several HSPs with lower subject coverage than blastn would report.
+native` runs the seed-and-extend search of wf_search.hip on one MI355X (DESIGN.md §12 states
+the rule): the contigs are indexed once (wf_map_index), the database genes stream through in
+chunks as subjects (wf_search), and the table is written in the reference's 15 columns.  It
+is not a blastn clone.  Without `--gapped` it reports ungapped HSPs only, so a diverged
+homolog with indels comes out as several HSPs with lower subject coverage than blastn would
+report.  With `--gapped` (wf_search_gapped, wf_search_gap.hip) every ungapped
+HSP is an anchor of a banded x-drop alignment with linear gap cost, and the table holds those
+alignments: one row for such a homolog, when no gap on one side of an anchor is longer than
+the band.
 
-Host side (this module): the streaming subject-FASTA reader, the calls into wf_search, the
-ordering and --max-target-seqs step and the row writer.
+Host side (this module): the streaming subject-FASTA reader, the calls into wf_search /
+wf_search_gapped, the ordering and --max-target-seqs step and the row writer.
 """
 from __future__ import annotations
 
@@ -36,6 +41,11 @@ BLAST_FORMAT = "6 qseqid sseqid qlen slen length qstart qend sstart send pident 
 RECORD_FIELDS = (("contig", np.int32), ("subject", np.int32), ("minus", np.uint8), ("qstart", np.int32),
                  ("sstart", np.int32), ("length", np.int32), ("matches", np.int32))
 STAT_FIELDS = ("seed_hits", "seeds_skipped", "raw_hsps")
+GAP_DEFAULTS = dict(band=15, xdrop_gap=30)
+GAP_RECORD_FIELDS = (("contig", np.int32), ("subject", np.int32), ("minus", np.uint8), ("qstart", np.int32),
+                     ("qspan", np.int32), ("sstart", np.int32), ("sspan", np.int32), ("length", np.int32),
+                     ("matches", np.int32), ("gaps", np.int32))
+GAP_STAT_FIELDS = STAT_FIELDS + ("anchors", "raw_alignments")
 
 
 class SearchError(inputs.InputError):
@@ -48,14 +58,16 @@ class SearchError(inputs.InputError):
 
 class Searcher:
     """One context with the index of one contig set; `search` runs wf_search on one chunk of
-    subjects and returns its records (RECORD_FIELDS, subject indices within the chunk)."""
+    subjects and returns its records (RECORD_FIELDS, subject indices within the chunk);
+    `search_gapped` runs wf_search_gapped (GAP_RECORD_FIELDS)."""
 
     def __init__(self, seq, off, seed_length=21, seed_stride=8, max_seed_hits=64, xdrop=20, min_score=28,
-                 device=0, capacity=1 << 16):
+                 device=0, capacity=1 << 16, band=15, xdrop_gap=30):
         self.params = L.WfSearchParams(seed_len=int(seed_length), stride=int(seed_stride),
                                        max_occ=int(max_seed_hits), xdrop=int(xdrop), min_score=int(min_score))
+        self.gap_params = L.WfSearchGapParams(band=int(band), xdrop_gap=int(xdrop_gap))
         self.capacity = max(int(capacity), 1)
-        self.stats = dict.fromkeys(STAT_FIELDS, 0)
+        self.stats = dict.fromkeys(GAP_STAT_FIELDS, 0)
         # the index's own max_occ belongs to the read mapper and is not read by the search
         self.mapper = mapper.Mapper(seq, off, seed_length=int(seed_length), device=device)
         self.so, self.h = self.mapper.so, self.mapper.h
@@ -86,6 +98,30 @@ class Searcher:
             raise L.WaafleHipError(rc, self.so.wf_last_error(self.mapper.h).decode())
         return out
 
+    def search_gapped_once(self, seq, off, capacity, params=None, gap_params=None):
+        """(return code, full record count, records written): one wf_search_gapped call."""
+        seq = np.ascontiguousarray(seq, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        out = {f: np.zeros(capacity, dt) for f, dt in GAP_RECORD_FIELDS}
+        sb = L.WfSearchSubjects(n_subjects=len(off) - 1, seq=L.ptr(seq), off=L.ptr(off))
+        r = L.WfSearchGapResult(capacity=capacity, **{f: L.ptr(out[f]) for f, _ in GAP_RECORD_FIELDS})
+        rc = self.so.wf_search_gapped(self.mapper.h, C.byref(sb), C.byref(params or self.params),
+                                      C.byref(gap_params or self.gap_params), C.byref(r))
+        if rc == L.WF_OK:
+            for f in GAP_STAT_FIELDS:
+                self.stats[f] += getattr(r, f)
+        n = int(r.n)
+        return rc, n, {f: a[:min(n, capacity)] for f, a in out.items()}
+
+    def search_gapped(self, seq, off, params=None, gap_params=None):
+        rc, n, out = self.search_gapped_once(seq, off, self.capacity, params, gap_params)
+        if rc == L.WF_E_NOMEM:                              # the call is repeatable with more room
+            self.capacity = max(n, 2 * self.capacity)
+            rc, n, out = self.search_gapped_once(seq, off, self.capacity, params, gap_params)
+        if rc != L.WF_OK:
+            raise L.WaafleHipError(rc, self.so.wf_last_error(self.mapper.h).decode())
+        return out
+
     def close(self):
         self.mapper.close()
 
@@ -96,11 +132,11 @@ class Searcher:
         self.close()
 
 
-def search_chunk(searcher, seq, off):
-    """`Searcher.search`; a chunk that is refused as too big (WF_E_TOOBIG) is halved, down to
-    one subject."""
+def search_chunk(searcher, seq, off, gapped=False):
+    """`Searcher.search` (gapped: `Searcher.search_gapped`); a chunk that is refused as too big
+    (WF_E_TOOBIG) is halved, down to one subject."""
     try:
-        return searcher.search(seq, off)
+        return searcher.search_gapped(seq, off) if gapped else searcher.search(seq, off)
     except L.WaafleHipError as exc:
         n = len(off) - 1
         if exc.code != L.WF_E_TOOBIG:
@@ -108,8 +144,8 @@ def search_chunk(searcher, seq, off):
         if n <= 1:
             raise SearchError("a single subject is too big to search: {}".format(exc.msg))
     h = n // 2
-    a = search_chunk(searcher, seq[:off[h]], off[:h + 1])
-    b = search_chunk(searcher, seq[off[h]:], off[h:] - off[h])
+    a = search_chunk(searcher, seq[:off[h]], off[:h + 1], gapped)
+    b = search_chunk(searcher, seq[off[h]:], off[h:] - off[h], gapped)
     b["subject"] = b["subject"] + np.int32(h)
     return {f: np.concatenate([a[f], b[f]]) for f in a}
 
@@ -173,13 +209,19 @@ def iter_subject_chunks(path, chunk_bases=CHUNK_BASES):
 # ---------------------------------------------------------------------------
 
 def score_of(rec):
-    return 3 * rec["matches"].astype(np.int64) - 2 * rec["length"].astype(np.int64)
+    """The raw score of ungapped records; of gapped ones (they have `gaps`) score2, the score
+    in half units: 2 per match, -4 per mismatch, -5 per gap column."""
+    m, length = rec["matches"].astype(np.int64), rec["length"].astype(np.int64)
+    if "gaps" in rec:
+        return 6 * m - 4 * length - rec["gaps"].astype(np.int64)
+    return 3 * m - 2 * length
 
 
 def order_records(rec, max_target_seqs=MAX_TARGET_SEQS):
     """Indices of the records to write, in the table's order: by contig; within a contig the
     subjects are ranked by (-best score, subject) and those past `max_target_seqs` lose their
-    rows; the rest go by (-score, subject, minus, qstart, sstart)."""
+    rows; the rest go by (-score, subject, minus, qstart, sstart), gapped records by (-score2,
+    subject, minus, qstart, sstart, qspan, sspan)."""
     n = len(rec["contig"])
     if n == 0:
         return np.zeros(0, np.int64)
@@ -195,8 +237,9 @@ def order_records(rec, max_target_seqs=MAX_TARGET_SEQS):
     keep_pair = np.zeros(len(pair), bool)
     keep_pair[o] = (np.arange(len(o)) - run) < max_target_seqs
     idx = np.flatnonzero(keep_pair[inv])
-    o2 = np.lexsort((rec["sstart"][idx], rec["qstart"][idx], rec["minus"][idx], subject[idx], -score[idx],
-                     contig[idx]))
+    spans = (rec["sspan"][idx], rec["qspan"][idx]) if "gaps" in rec else ()
+    o2 = np.lexsort(spans + (rec["sstart"][idx], rec["qstart"][idx], rec["minus"][idx], subject[idx], -score[idx],
+                             contig[idx]))
     return idx[o2]
 
 
@@ -208,8 +251,21 @@ def bitscore_text(score):
 def format_rows(rec, order, contig_names, contig_lens, subject_ids, subject_lens, db_bases):
     """The 15 columns of utils.c_blast_fields, tab-separated, 1-based; a minus HSP has
     descending subject coordinates.  evalue = K qlen D exp(-LAMBDA score), D the database's
-    bases: no length adjustment, not BLAST's effective-length value."""
+    bases: no length adjustment, not BLAST's effective-length value.  Gapped records: length
+    counts the alignment's columns, the gaps column holds the gap columns and the score is
+    score2 / 2, which may end in .5."""
     out = []
+    if "gaps" in rec:
+        cols = [rec[f][order].tolist() for f, _ in GAP_RECORD_FIELDS]
+        for c, g, minus, qs, qn, ss, sn, length, m, gaps in zip(*cols):
+            score, M, qlen = (6 * m - 4 * length - gaps) / 2, int(subject_lens[g]), int(contig_lens[c])
+            s0, s1 = (M - ss, M - ss - sn + 1) if minus else (ss + 1, ss + sn)
+            ev = K * qlen * db_bases * math.exp(-LAMBDA * score)
+            out.append("\t".join(str(v) for v in (
+                contig_names[c], subject_ids[g], qlen, M, length, qs + 1, qs + qn, s0, s1,
+                "%.3f" % (100.0 * m / length), m, gaps, "%.2e" % ev, bitscore_text(score),
+                "minus" if minus else "plus")))
+        return out
     cols = [rec[f][order].tolist() for f, _ in RECORD_FIELDS]
     for c, g, minus, qs, ss, length, m in zip(*cols):
         score, M, qlen = 3 * m - 2 * length, int(subject_lens[g]), int(contig_lens[c])
@@ -223,21 +279,23 @@ def format_rows(rec, order, contig_names, contig_lens, subject_ids, subject_lens
 
 
 def search_files(query, db, out_path, device=0, chunk_bases=CHUNK_BASES, max_target_seqs=MAX_TARGET_SEQS,
-                 say=lambda *a: None, **params):
-    """The native search of the FASTA `db` against the contigs `query`, written to `out_path`.
+                 say=lambda *a: None, gapped=False, band=15, xdrop_gap=30, **params):
+    """The native search of the FASTA `db` against the contigs `query`, written to `out_path`;
+    gapped: the alignments of the gapped extension in place of the ungapped HSPs.
     Returns the searcher's counters plus rows, subjects and database bases."""
+    fields = GAP_RECORD_FIELDS if gapped else RECORD_FIELDS
     names, seq, off = mapper.read_fasta(query)
     ids, lens, parts = [], [], []
-    with Searcher(seq, off, device=device, **params) as s:
+    with Searcher(seq, off, device=device, band=band, xdrop_gap=xdrop_gap, **params) as s:
         for cid, cseq, coff in iter_subject_chunks(db, chunk_bases):
-            rec = search_chunk(s, cseq, coff)
+            rec = search_chunk(s, cseq, coff, gapped)
             rec["subject"] = rec["subject"] + np.int32(len(ids))
             parts.append(rec)
             ids += cid
             lens.append(np.diff(coff))
             say("  {:,} subjects searched, {:,} records".format(len(ids), sum(len(p["contig"]) for p in parts)))
         stats = dict(s.stats)
-    rec = {f: np.concatenate([p[f] for p in parts]) if parts else np.zeros(0, dt) for f, dt in RECORD_FIELDS}
+    rec = {f: np.concatenate([p[f] for p in parts]) if parts else np.zeros(0, dt) for f, dt in fields}
     lens = np.concatenate(lens) if lens else np.zeros(0, np.int64)
     order = order_records(rec, max_target_seqs)
     rows = format_rows(rec, order, names, np.diff(off), ids, lens, int(lens.sum()))
@@ -254,7 +312,8 @@ def search_files(query, db, out_path, device=0, chunk_bases=CHUNK_BASES, max_tar
 def build_parser():
     ap = argparse.ArgumentParser(
         description="Step 1 in the WAAFLE pipeline: search a set of contigs against a WAAFLE database,\n"
-                    "with blastn (the reference's command) or with the built-in ungapped GPU search.",
+                    "with blastn (the reference's command) or with the built-in GPU search (ungapped, or\n"
+                    "with --gapped the banded gapped extension of its HSPs).",
         formatter_class=argparse.RawTextHelpFormatter)
     ap.add_argument("query", help="contigs file (fasta format)")
     ap.add_argument("db", help="path to WAAFLE BLAST database; with --searcher native: the genes' FASTA\n"
@@ -267,8 +326,9 @@ def build_parser():
     ap.add_argument("--out", default=None, metavar="<path>",
                     help="path for blast output file\n[default: <derived from input>]")
     ap.add_argument("--searcher", choices=["blastn", "native"], default="blastn",
-                    help="blastn: run the reference's blastn command; native: the built-in ungapped\n"
-                         "seed-and-extend search on the GPU (not a blastn clone)\n[default: blastn]")
+                    help="blastn: run the reference's blastn command; native: the built-in\n"
+                         "seed-and-extend search on the GPU (not a blastn clone; ungapped HSPs unless\n"
+                         "--gapped is given)\n[default: blastn]")
     g = ap.add_argument_group("native search (defaults are choices, not measured optima)")
     g.add_argument("--seed-length", type=int, default=DEFAULTS["seed_length"], metavar="<12..32>")
     g.add_argument("--seed-stride", type=int, default=DEFAULTS["seed_stride"], metavar="<1..32>")
@@ -281,6 +341,13 @@ def build_parser():
     g.add_argument("--chunk-bases", type=int, default=CHUNK_BASES, metavar="<int>",
                    help="subject bases per device call")
     g.add_argument("--gpu", type=int, default=0, metavar="<int>")
+    g.add_argument("--gapped", action="store_true",
+                   help="extend every ungapped HSP by a banded x-drop alignment with linear gap cost\n"
+                        "(match +1, mismatch -2, gap column -2.5) and report those alignments\n[default: off]")
+    g.add_argument("--band", type=int, default=GAP_DEFAULTS["band"], metavar="<1..31>",
+                   help="--gapped: diagonals either way of the anchor's, per side")
+    g.add_argument("--xdrop-gap", type=int, default=GAP_DEFAULTS["xdrop_gap"], metavar="<1..1000>",
+                   help="--gapped: x-drop of the gapped extension, raw score")
     return ap
 
 
@@ -318,7 +385,8 @@ def main(argv=None):
         stats = search_files(args.query, args.db, args.out, device=args.gpu, chunk_bases=args.chunk_bases,
                              max_target_seqs=args.max_target_seqs, say=inputs.say,
                              seed_length=args.seed_length, seed_stride=args.seed_stride,
-                             max_seed_hits=args.max_seed_hits, xdrop=args.xdrop, min_score=args.min_score)
+                             max_seed_hits=args.max_seed_hits, xdrop=args.xdrop, min_score=args.min_score,
+                             gapped=args.gapped, band=args.band, xdrop_gap=args.xdrop_gap)
     except (inputs.InputError, OSError, L.WaafleHipError) as exc:
         die(str(exc))
     inputs.say("Finished successfully ({:,} rows from {:,} subjects; {:,} seed hits).".format(
