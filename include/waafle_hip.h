@@ -30,7 +30,8 @@ extern "C" {
                                     WF_OPT_WAVE_TWO 0 (the round-3 hand-over flow) retired;
                                     still 6 (additive): wf_map_index, wf_map_pairs;
                                     still 6 (additive): wf_map_pairs_gapped;
-                                    still 6 (additive): wf_search, wf_search_gapped */
+                                    still 6 (additive): wf_search, wf_search_gapped;
+                                    still 6 (additive): wf_search_mask */
 
 enum wf_status {
   WF_OK = 0,
@@ -482,6 +483,39 @@ typedef struct wf_search_gap_result { /* caller-owned host arrays of `capacity` 
    unaffected.  Returns after the work is done. */
 int wf_search_gapped(wf_ctx* ctx, const wf_search_subjects* subjects, const wf_search_params* params,
                      const wf_search_gap_params* gap_params, wf_search_gap_result* out);
+
+/* Low-complexity masking.  wf_search_mask computes the symmetric-DUST mask
+ * (Morgulis et al. 2006, the published definition) of the contigs the context holds and
+ * rebuilds the index, at the seed length it has, without the S-mers that hold a masked base:
+ * a soft mask, as blastn applies to its query by default.  Masked stretches then give no
+ * seeds, and max_occ counts the remaining occurrences only; the extensions of wf_search and
+ * wf_search_gapped read the bases as before and run through masked stretches, and the N plane
+ * is unchanged.  A run is a maximal stretch of A/C/G/T inside one contig; an interval of l
+ * triplets (l + 2 <= window bases) of one run scores r / (l - 1), r the sum of c (c - 1) / 2
+ * over the counts c of the 64 triplet kinds (0 for l = 1); it is perfect when 10 r >
+ * level (l - 1) and no sub-interval scores strictly more; a base is masked iff a perfect
+ * interval covers it.  Not a dustmasker clone: agreement with NCBI dustmasker is not measured.
+ * The mask lasts until the next wf_map_index on the context, which builds an unmasked index
+ * again; calling wf_search_mask again replaces the mask.  wf_map_pairs on the same context
+ * sees the masked index too: give the read mapper a context of its own. */
+typedef struct wf_dust_params {
+  int32_t window;             /* Wd, 8..64 bases (default 64) */
+  int32_t level;              /* Lv >= 1; the score threshold is Lv / 10 (default 20) */
+  int32_t _pad[2];
+} wf_dust_params;
+
+typedef struct wf_dust_result {
+  uint32_t* mask;             /* null, or caller-owned host memory of (total + 31) / 32 words,
+                                 total = the contigs' bases: bit p & 31 of word p >> 5 is set
+                                 iff store position p (contigs concatenated) is masked */
+  int64_t masked_bases;       /* out */
+  int64_t kmers_before;       /* out: S-mers of the index without a mask, */
+  int64_t kmers_after;        /*   and of the index as it is now         */
+} wf_dust_result;
+
+/* WF_E_STATE before wf_map_index; WF_E_BADINPUT for window outside 8..64 or level < 1.
+   Returns after the work is done. */
+int wf_search_mask(wf_ctx* ctx, const wf_dust_params* params, wf_dust_result* out);
 
 /* ---- --write-details (orgscorer.py:766-812, 931-937) --------------------------------
  * With details on, the next wf_score (staged mode) also records, for every roll-up level,

@@ -3,7 +3,8 @@ one MI355X.
 
     python scripts/search_bench.py [--contigs 10000 --contig-length 5000 --db-bases 200000000
                                     --subject-length 1000 --homolog-share 0.01 --chunk-bases 67108864
-                                    --indel-rate 0.003 --gapped --band 15 --xdrop-gap 30]
+                                    --indel-rate 0.003 --gapped --band 15 --xdrop-gap 30
+                                    --low-complexity 2000 --dust]
 
 Not bench.py (the flagship workload); the numbers go to DESIGN.md §12 and profiles/search/.
 The workload is seeded: random contigs, and a database of random subjects of which a share
@@ -11,7 +12,11 @@ The workload is seeded: random contigs, and a database of random subjects of whi
 90..100 % identity; with --indel-rate r every planted homolog also gets Poisson(r x length)
 indels of 1..6 bases, half insertions, half deletions (its length stays --subject-length: it
 is cut longer and trimmed).  --gapped runs `Searcher.search_gapped` in place of
-`Searcher.search`.  The search parameters are the defaults (S 21, T 8, max_occ 64, X 20,
+`Searcher.search`.  --low-complexity n writes n low-complexity stretches (homopolymers and
+2..4-base repeats of 30..80 bases) over bases of the contigs and n over random subjects; --dust
+masks the contigs (`wf_search_mask`) before the search and reports the mask's
+counters and the wall of that call (mask kernel, index rebuild and the mask's copy to the
+host).  The search parameters are the defaults (S 21, T 8, max_occ 64, X 20,
 min_score 28).  The GPU step runs in a child process under its own time limit
 (--step-timeout); when it fails or runs out of time nothing more is started.
 
@@ -53,6 +58,9 @@ def parse(argv=None):
     ap.add_argument("--gapped", action="store_true", help="wf_search_gapped in place of wf_search")
     ap.add_argument("--band", type=int, default=15)
     ap.add_argument("--xdrop-gap", type=int, default=30)
+    ap.add_argument("--low-complexity", type=int, default=0,
+                    help="low-complexity stretches written over the contigs, and as many over random subjects")
+    ap.add_argument("--dust", action="store_true", help="wf_search_mask on the contigs before the search")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--gpu", type=int, default=0)
     ap.add_argument("--step", choices=["search"], help="run the step in this process")
@@ -91,6 +99,20 @@ def make_workload(a):
     minus = rng.random(len(hom)) < 0.5
     cut[minus] = 3 - cut[minus][:, ::-1]
     subj[hom] = cut
+    if a.low_complexity > 0:                                  # a stream of its own: 0 is the old workload
+        rng3 = np.random.default_rng(a.seed + 2)
+        rows = np.setdiff1d(np.arange(n), hom)
+        for where in ("contigs", "subjects"):
+            for _ in range(a.low_complexity):
+                unit = rng3.integers(0, 4, int(rng3.integers(1, 5)), dtype=np.uint8)
+                m = int(rng3.integers(30, 81))
+                rep = np.tile(unit, m // len(unit) + 1)[:m]
+                if where == "contigs":
+                    at = off[int(rng3.integers(0, a.contigs))] + int(rng3.integers(0, a.contig_length - m + 1))
+                    codes[at:at + m] = rep
+                else:
+                    at = int(rng3.integers(0, L - m + 1))
+                    subj[rows[int(rng3.integers(0, len(rows)))], at:at + m] = rep
     return codes, off, subj, hom
 
 
@@ -101,7 +123,16 @@ def step_search(a):
     per = max(a.chunk_bases // L, 1)
     walls, records, found, span = [], 0, np.zeros(n, bool), np.zeros(n, np.int64)
     gap = dict(band=a.band, xdrop_gap=a.xdrop_gap) if a.gapped else {}
+    dust = {}
     with search.Searcher(ASCII[codes], off, device=a.gpu, **gap) as s:
+        if a.dust:
+            t0 = time.perf_counter()
+            s.apply_mask(len(codes))
+            dust = dict(s.dust_stats, mask_call_s=time.perf_counter() - t0,
+                        masked_fraction=s.dust_stats["masked_bases"] / max(len(codes), 1))
+            t0 = time.perf_counter()
+            s.apply_mask(len(codes))                          # again, with everything allocated
+            dust["mask_call_again_s"] = time.perf_counter() - t0
         run = s.search_gapped if a.gapped else s.search
         w = min(n, max((1 << 20) // L, 1))
         run(ASCII[subj[:w]].reshape(-1), np.arange(w + 1, dtype=np.int64) * L)          # warm-up chunk
@@ -124,7 +155,7 @@ def step_search(a):
                 anchors=stats.get("anchors", 0), raw_alignments=stats.get("raw_alignments", 0),
                 other_subjects_with_records=int(found.sum() - found[hom].sum()), records=records,
                 seed_hits=stats["seed_hits"], seeds_skipped=stats["seeds_skipped"], raw_hsps=stats["raw_hsps"],
-                skipped_share=stats["seeds_skipped"] / max(stats["seed_hits"], 1),
+                skipped_share=stats["seeds_skipped"] / max(stats["seed_hits"], 1), dust=dust,
                 timing="host-resident subjects: copies in and out and the host's de-duplication included, "
                        "one warm-up chunk")
 
@@ -137,7 +168,7 @@ def main(argv=None):
     out = dict(workload=dict(contigs=a.contigs, contig_length=a.contig_length, db_bases=a.db_bases,
                              subject_length=a.subject_length, homolog_share=a.homolog_share,
                              identity="90..100 %", indel_rate=a.indel_rate, seed=a.seed, gapped=a.gapped,
-                             band=a.band, xdrop_gap=a.xdrop_gap,
+                             band=a.band, xdrop_gap=a.xdrop_gap, low_complexity=a.low_complexity, dust=a.dust,
                              params=dict(seed_length=21, seed_stride=8, max_seed_hits=64, xdrop=20, min_score=28)))
     passed = [x for x in (argv if argv is not None else sys.argv[1:])]
     cmd = [sys.executable, os.path.abspath(__file__), "--step", "search"] + passed

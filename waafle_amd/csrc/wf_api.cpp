@@ -854,6 +854,25 @@ int wf_search_gapped(wf_ctx* ctx, const wf_search_subjects* sb, const wf_search_
   return WF_OK;
 }
 
+int wf_search_mask(wf_ctx* ctx, const wf_dust_params* p, wf_dust_result* r) {
+  if (!ctx) return WF_E_BADINPUT;
+  if (!p || !r) return fail(ctx, WF_E_BADINPUT, "null params/result");
+  r->masked_bases = r->kmers_before = r->kmers_after = 0;
+  if (p->window < 8 || p->window > 64) return fail(ctx, WF_E_BADINPUT, "window %d outside 8..64", p->window);
+  if (p->level < 1) return fail(ctx, WF_E_BADINPUT, "level %d below 1", p->level);
+  int S = 0, occ = 0;
+  if (!wf::map_index_params(ctx->map, &S, &occ)) return fail(ctx, WF_E_STATE, "wf_search_mask before wf_map_index");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  wf::DustStats stats{0, 0, 0};
+  std::string err;
+  const int rc = wf::dust_mask(ctx->map, p->window, p->level, &stats, r->mask, ctx->stream, &err);
+  if (rc) return fail(ctx, rc, "%s", err.c_str());
+  r->masked_bases = stats.masked_bases;
+  r->kmers_before = stats.kmers_before;
+  r->kmers_after = stats.kmers_after;
+  return WF_OK;
+}
+
 int wf_details_enable(wf_ctx* ctx, int on) {
   if (!ctx) return WF_E_BADINPUT;
   ctx->details_on = on != 0;

@@ -218,6 +218,15 @@ int search_gapped_run(MapState* st, const char* seq, const int64_t* off, int64_t
                       int band, int xdrop_gap, const SearchGapOut& out, int64_t* n, SearchStats* stats,
                       SearchGapStats* gstats, hipStream_t s, std::string* err);
 
+// low-complexity mask (wf_dust.hip): the symmetric-DUST mask of the contigs
+// the state holds, kept in the state, and the index rebuilt without the S-mers that hold a
+// masked base.  host_mask: null, or (total + 31) / 32 words for the mask.  0, or -2 with the
+// message in *err; after a failure the state has no index.
+constexpr int kDustTile = 448;               // start positions one block of k_dust_mask emits
+struct DustStats { int64_t masked_bases, kmers_before, kmers_after; };
+int dust_mask(MapState* st, int window, int level, DustStats* stats, uint32_t* host_mask, hipStream_t s,
+              std::string* err);
+
 // --write-details: per roll-up level, the evaluated (active) contigs and the segment
 // records of the level, copied to the host (wf_staged.hip details_level)
 struct DetailsLevel {

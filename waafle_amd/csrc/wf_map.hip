@@ -7,6 +7,7 @@
 //                 (x: low bit, y: high bit of the base code A0 C1 G2 T3) and a 1-bit N plane;
 //                 the store is padded so the window read of words w and w + 1 stays in bounds
 //   k_map_flag    thread per position: 1 when the S-mer there has no N and stays in its contig
+//                 (k_map_flag_masked: and holds no base of the low-complexity mask, wf_dust.hip)
 //   k_map_emit    (device scan of the flags) -> compact (key, position) pairs, position order;
 //                 key = high-plane bits << S | low-plane bits
 //   device radix sort on the 2S key bits (stable: equal keys keep ascending positions)
@@ -68,6 +69,19 @@ __global__ void k_map_flag(const MapIndexView ix, int n_pos, int32_t* flag) {
   uint64_t key;
   const int c = contig_of(ix.coff, ix.n_contigs, q);
   flag[q] = (int64_t)q + ix.S <= ix.coff[c + 1] && store_kmer(ix, q, &key);
+}
+
+// k_map_flag for an index with a low-complexity mask (wf_search_mask): the S bases must be
+// unmasked in dm too.  A kernel of its own, so that the mapper's k_map_flag stays as it is.
+__global__ void k_map_flag_masked(const MapIndexView ix, const uint32_t* dm, int n_pos, int32_t* flag) {
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= n_pos) return;
+  uint64_t key;
+  const int c = contig_of(ix.coff, ix.n_contigs, q);
+  const int W = q >> 5, sh = q & 31;
+  const uint32_t mask = ix.S == 32 ? 0xFFFFFFFFu : (1u << ix.S) - 1u;
+  flag[q] = (int64_t)q + ix.S <= ix.coff[c + 1] && store_kmer(ix, q, &key) &&
+            (window32(dm[W], dm[W + 1], sh) & mask) == 0;
 }
 
 __global__ void k_map_emit(const MapIndexView ix, int n_pos, const int32_t* flag, const int32_t* slot,
@@ -560,7 +574,7 @@ void map_destroy(MapState* st) {
   MapBuf* bufs[] = {&st->pk, &st->nm, &st->coff, &st->keys, &st->kpos, &st->bucket, &st->s1, &st->o1,
                     &st->s2, &st->o2, &st->r_contig, &st->r_pos1, &st->r_pos2, &st->r_strand, &st->r_mm1,
                     &st->r_mm2, &st->r_d1, &st->r_d2, &st->r_k1, &st->r_k2, &st->r_flags, &st->g_flag,
-                    &st->g_slot, &st->g_idx, &st->g_tmp};
+                    &st->g_slot, &st->g_idx, &st->g_tmp, &st->dm};
   for (MapBuf* b : bufs) map_release(*b);
   search_destroy(st->search);
   delete st;
@@ -582,18 +596,13 @@ int map_index(MapState* st, const char* seq, const int64_t* off, int n_contigs, 
     return -7;
   }
   st->have_index = false;
+  st->have_mask = false;
   (void)hipStreamSynchronize(s);         // a device-resident map_pairs may still read the old index
   std::vector<int32_t> coff((size_t)n_contigs + 1, 0);
   for (int c = 0; c <= n_contigs && n_contigs > 0; ++c) coff[c] = (int32_t)off[c];
   const int64_t words = (total + 31) / 32 + 2;
-  const int n_pos = (int)std::max<int64_t>(total - seed_len + 1, 0);
-  MapBuf d_seq, d_flag, d_slot, d_keys, d_kpos, d_tmp;
+  MapBuf d_seq;
   int rc = 0;
-  int32_t last_flag = 0, last_slot = 0;
-  int64_t nk = 0;
-  int bits = 0;
-  size_t tmp_bytes = 0;
-  MapIndexView ix{};
   MAP_RC(map_ensure(st->pk, (size_t)words * sizeof(uint2), err));
   MAP_RC(map_ensure(st->nm, (size_t)words * sizeof(uint32_t), err));
   MAP_RC(map_ensure(st->coff, coff.size() * sizeof(int32_t), err));
@@ -608,12 +617,34 @@ int map_index(MapState* st, const char* seq, const int64_t* off, int n_contigs, 
   st->seed_len = seed_len;
   st->max_occ = max_occ;
   st->total = total;
-  ix = map_view(st);
+  MAP_RC(map_build_index(st, nullptr, s, err));
+  st->n_kmers_plain = st->n_kmers;
+  st->have_index = true;
+done:
+  if (rc) (void)hipStreamSynchronize(s);
+  map_release(d_seq);
+  return rc;
+}
+
+int map_build_index(MapState* st, const uint32_t* dm, hipStream_t s, std::string* err) {
+  const int seed_len = st->seed_len;
+  const int n_pos = (int)std::max<int64_t>(st->total - seed_len + 1, 0);
+  MapBuf d_flag, d_slot, d_keys, d_kpos, d_tmp;
+  int rc = 0;
+  int32_t last_flag = 0, last_slot = 0;
+  int64_t nk = 0;
+  int bits = 0;
+  size_t tmp_bytes = 0;
+  const MapIndexView ix = map_view(st);
   if (n_pos > 0) {
     MAP_RC(map_ensure(d_flag, (size_t)n_pos * sizeof(int32_t), err));
     MAP_RC(map_ensure(d_slot, (size_t)n_pos * sizeof(int32_t), err));
-    hipLaunchKernelGGL(k_map_flag, dim3((unsigned)((n_pos + 255) / 256)), dim3(256), 0, s, ix, n_pos,
-                       static_cast<int32_t*>(d_flag.p));
+    if (dm)
+      hipLaunchKernelGGL(k_map_flag_masked, dim3((unsigned)((n_pos + 255) / 256)), dim3(256), 0, s, ix, dm, n_pos,
+                         static_cast<int32_t*>(d_flag.p));
+    else
+      hipLaunchKernelGGL(k_map_flag, dim3((unsigned)((n_pos + 255) / 256)), dim3(256), 0, s, ix, n_pos,
+                         static_cast<int32_t*>(d_flag.p));
     MAP_TRY(hipGetLastError());
     MAP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, static_cast<const int32_t*>(d_flag.p),
                                              static_cast<int32_t*>(d_slot.p), n_pos, s));
@@ -659,10 +690,9 @@ int map_index(MapState* st, const char* seq, const int64_t* off, int n_contigs, 
                      static_cast<uint32_t*>(st->bucket.p));
   MAP_TRY(hipGetLastError());
   MAP_TRY(hipStreamSynchronize(s));
-  st->have_index = true;
 done:
   if (rc) (void)hipStreamSynchronize(s);
-  for (MapBuf* b : {&d_seq, &d_flag, &d_slot, &d_keys, &d_kpos, &d_tmp}) map_release(*b);
+  for (MapBuf* b : {&d_flag, &d_slot, &d_keys, &d_kpos, &d_tmp}) map_release(*b);
   return rc;
 }
 

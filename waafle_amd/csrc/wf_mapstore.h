@@ -23,6 +23,12 @@ struct MapState {
   int n_contigs = 0, seed_len = 0, max_occ = 0, bshift = 0;
   int64_t total = 0, n_kmers = 0;
   bool have_index = false;
+  // the low-complexity mask of the contigs (wf_dust.hip, wf_search_mask): one bit per store
+  // position, laid out as nm.  have_mask: the index holds only the S-mers without a masked
+  // base; map_index clears it.  n_kmers_plain: the S-mers of the index without a mask.
+  MapBuf dm;
+  bool have_mask = false;
+  int64_t n_kmers_plain = 0;
   // read staging (host-resident calls)
   MapBuf s1, o1, s2, o2, r_contig, r_pos1, r_pos2, r_strand, r_mm1, r_mm2;
   // the gapped pass: its result staging and the list of pairs to rescue
@@ -32,6 +38,11 @@ struct MapState {
 };
 
 void search_destroy(SearchState* ss);
+
+// (wf_map.hip) The S-mer index of the store the state holds, built anew: flag, scan, emit,
+// sort, bucket.  dm null: every S-mer without an N that stays in its contig; else only those
+// whose S bases are all unmasked in dm.  Sets keys, kpos, bucket, bshift and n_kmers.
+int map_build_index(MapState* st, const uint32_t* dm, hipStream_t s, std::string* err);
 
 namespace {
 
@@ -43,6 +54,7 @@ struct MapIndexView {
   const int32_t* kpos;        // [n_kmers] position of each sorted S-mer
   const uint32_t* bucket;     // [2^bits + 1]
   int n_contigs, S, bshift;
+  const uint32_t* dm;         // [words + 2] low-complexity mask plane; null: no mask
 };
 
 // A0 C1 G2 T3, anything else 4 (N); lower case counts as upper
@@ -141,6 +153,7 @@ MapIndexView map_view(const MapState* st) {
   ix.n_contigs = st->n_contigs;
   ix.S = st->seed_len;
   ix.bshift = st->bshift;
+  ix.dm = st->have_mask ? static_cast<const uint32_t*>(st->dm.p) : nullptr;
   return ix;
 }
 

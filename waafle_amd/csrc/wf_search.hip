@@ -1,7 +1,8 @@
 // Homology search on MI355X (gfx950): ungapped seed-and-extend of database genes (the
 // subjects, streamed in chunks) against the contigs the mapper's index holds (wf_map_index).
 // DESIGN.md §12 states the rule; tests/search_oracle.py restates it on the CPU.  Not a blastn
-// clone: ungapped HSPs only, no masking, no composition statistics.
+// clone: ungapped HSPs only, no composition statistics; masking only after wf_search_mask
+// (wf_dust.hip), which takes the low-complexity S-mers out of the index.
 //
 // One chunk (search_run):
 //   k_map_pack / k_search_pack_rc  the chunk as bit planes (wf_mapstore.h) in both orientations:
@@ -203,10 +204,17 @@ __global__ __launch_bounds__(256) void k_search_extend(const SearchArgs A) {
   const int D = q - sd.a;                        // store position of variant column 0
   const int S = ix.S, T = A.T;
   // the predecessor a - T on this diagonal is a seed hit when its seed is usable and the T
-  // columns before this seed match inside the contig: it yields the same HSP
+  // columns before this seed match inside the contig: it yields the same HSP.  With a
+  // low-complexity mask the index lacks the occurrences that hold a masked base, so the
+  // occurrence at q - T counts only when its S bases are unmasked.
   if (sd.a >= T && j > 0 && A.cnt[j - 1] > 0 && q - T >= c0) {
     uint32_t mis = search_mis(A, sd.strand, sd.vbase + sd.a - T, q - T);
     if (T < 32) mis &= (1u << T) - 1u;
+    if (ix.dm) {                                 // q - T >= 0; words W, W + 1 are in the plane
+      const int W = (q - T) >> 5, sh = (q - T) & 31;
+      const uint32_t smask = S == 32 ? 0xFFFFFFFFu : (1u << S) - 1u;
+      mis |= window32(ix.dm[W], ix.dm[W + 1], sh) & smask;
+    }
     if (mis == 0) {
       atomicAdd(&A.ctr[1], 1ull);
       return;

@@ -153,6 +153,15 @@ class WfSearchGapResult(C.Structure):
                 ("anchors", C.c_int64), ("raw_alignments", C.c_int64)]
 
 
+class WfDustParams(C.Structure):
+    _fields_ = [("window", C.c_int32), ("level", C.c_int32), ("_pad", C.c_int32 * 2)]
+
+
+class WfDustResult(C.Structure):
+    _fields_ = [("mask", _P), ("masked_bases", C.c_int64), ("kmers_before", C.c_int64),
+                ("kmers_after", C.c_int64)]
+
+
 class WfDetails(C.Structure):
     _fields_ = [("n_evals", C.c_int64), ("eval_contig", _P), ("eval_level", _P),
                 ("n_segs", C.c_int64), ("seg_level", _P), ("seg_contig", _P), ("seg_clade", _P),
@@ -192,6 +201,7 @@ SIGNATURES = {
                             C.POINTER(WfSearchResult)]),
     "wf_search_gapped": (C.c_int, [C.c_void_p, C.POINTER(WfSearchSubjects), C.POINTER(WfSearchParams),
                                    C.POINTER(WfSearchGapParams), C.POINTER(WfSearchGapResult)]),
+    "wf_search_mask": (C.c_int, [C.c_void_p, C.POINTER(WfDustParams), C.POINTER(WfDustResult)]),
     "wf_details_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "wf_details_read": (C.c_int, [C.c_void_p, C.POINTER(WfDetails)]),
 }

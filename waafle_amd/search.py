@@ -3,6 +3,7 @@
     python -m waafle_amd.search contigs.fna waafledb [--out --threads --blastn]
     python -m waafle_amd.search contigs.fna genes.fna --searcher native [--seed-length 21 ...]
     python -m waafle_amd.search contigs.fna genes.fna --searcher native --gapped [--band 15 --xdrop-gap 30]
+    python -m waafle_amd.search contigs.fna genes.fna --searcher native --dust [--dust-out masked.tsv]
 
 `--searcher blastn` (the default) issues exactly the reference's blastn command.  `--searcher
 native` runs the seed-and-extend search of wf_search.hip on one MI355X (DESIGN.md §12 states
@@ -13,7 +14,10 @@ homolog with indels comes out as several HSPs with lower subject coverage than b
 report.  With `--gapped` (wf_search_gapped, wf_search_gap.hip) every ungapped
 HSP is an anchor of a banded x-drop alignment with linear gap cost, and the table holds those
 alignments: one row for such a homolog, when no gap on one side of an anchor is longer than
-the band.
+the band.  With `--dust` (wf_search_mask, wf_dust.hip) the contigs'
+low-complexity stretches, by the published symmetric-DUST definition, give no seeds (a soft
+mask: extensions run through them); blastn masks its query so by default, this search only
+when asked, and agreement with NCBI dustmasker is not measured.
 
 Host side (this module): the streaming subject-FASTA reader, the calls into wf_search /
 wf_search_gapped, the ordering and --max-target-seqs step and the row writer.
@@ -46,6 +50,8 @@ GAP_RECORD_FIELDS = (("contig", np.int32), ("subject", np.int32), ("minus", np.u
                      ("qspan", np.int32), ("sstart", np.int32), ("sspan", np.int32), ("length", np.int32),
                      ("matches", np.int32), ("gaps", np.int32))
 GAP_STAT_FIELDS = STAT_FIELDS + ("anchors", "raw_alignments")
+DUST_DEFAULTS = dict(dust_window=64, dust_level=20)
+DUST_TILE = 448                  # kDustTile (csrc/wf_internal.h): starts one block of k_dust_mask emits
 
 
 class SearchError(inputs.InputError):
@@ -59,21 +65,54 @@ class SearchError(inputs.InputError):
 class Searcher:
     """One context with the index of one contig set; `search` runs wf_search on one chunk of
     subjects and returns its records (RECORD_FIELDS, subject indices within the chunk);
-    `search_gapped` runs wf_search_gapped (GAP_RECORD_FIELDS)."""
+    `search_gapped` runs wf_search_gapped (GAP_RECORD_FIELDS).  dust: the index holds no S-mer
+    with a low-complexity base (wf_search_mask after every indexing); the searcher owns its
+    context, so no read mapper sees that index."""
 
     def __init__(self, seq, off, seed_length=21, seed_stride=8, max_seed_hits=64, xdrop=20, min_score=28,
-                 device=0, capacity=1 << 16, band=15, xdrop_gap=30):
+                 device=0, capacity=1 << 16, band=15, xdrop_gap=30, dust=False, dust_window=64, dust_level=20):
         self.params = L.WfSearchParams(seed_len=int(seed_length), stride=int(seed_stride),
                                        max_occ=int(max_seed_hits), xdrop=int(xdrop), min_score=int(min_score))
         self.gap_params = L.WfSearchGapParams(band=int(band), xdrop_gap=int(xdrop_gap))
         self.capacity = max(int(capacity), 1)
-        self.stats = dict.fromkeys(GAP_STAT_FIELDS, 0)
+        self.stats = dict.fromkeys(GAP_STAT_FIELDS + ("masked_bases",), 0)
+        self.dust = bool(dust)
+        self.dust_params = L.WfDustParams(window=int(dust_window), level=int(dust_level))
+        self.dust_stats = None
+        self._mask = None
         # the index's own max_occ belongs to the read mapper and is not read by the search
         self.mapper = mapper.Mapper(seq, off, seed_length=int(seed_length), device=device)
         self.so, self.h = self.mapper.so, self.mapper.h
+        if self.dust:
+            try:
+                self.apply_mask(len(seq))
+            except Exception:
+                self.close()
+                raise
 
     def index(self, seq, off):
         self.mapper.index(seq, off)
+        self._mask, self.dust_stats, self.stats["masked_bases"] = None, None, 0
+        if self.dust:
+            self.apply_mask(len(seq))
+
+    def apply_mask(self, total, params=None):
+        """wf_search_mask on the `total` bases the context holds: the mask is kept for `mask`,
+        the call's counters in `dust_stats`."""
+        words = np.zeros((int(total) + 31) // 32, np.uint32)
+        r = L.WfDustResult(mask=L.ptr(words))
+        rc = self.so.wf_search_mask(self.mapper.h, C.byref(params or self.dust_params), C.byref(r))
+        if rc != L.WF_OK:
+            raise L.WaafleHipError(rc, self.so.wf_last_error(self.mapper.h).decode())
+        bits = np.unpackbits(words.view(np.uint8), bitorder="little")[:int(total)].astype(bool)
+        self._mask = bits
+        self.dust_stats = dict(masked_bases=int(r.masked_bases), kmers_before=int(r.kmers_before),
+                               kmers_after=int(r.kmers_after))
+        self.stats["masked_bases"] = int(r.masked_bases)
+
+    def mask(self):
+        """One bool per store base (the contigs concatenated), or None without a mask."""
+        return self._mask
 
     def search_once(self, seq, off, capacity, params=None):
         """(return code, full record count, records written): one wf_search call."""
@@ -148,6 +187,23 @@ def search_chunk(searcher, seq, off, gapped=False):
     b = search_chunk(searcher, seq[off[h]:], off[h:] - off[h], gapped)
     b["subject"] = b["subject"] + np.int32(h)
     return {f: np.concatenate([a[f], b[f]]) for f in a}
+
+
+def mask_intervals(mask, off):
+    """(contig, start, end) rows of the masked stretches, 0-based and half-open on the contig,
+    in store order; a stretch that runs over a contig's end is split there."""
+    rows = []
+    mask = np.asarray(mask, bool)
+    for c in range(len(off) - 1):
+        m = np.concatenate([[False], mask[int(off[c]):int(off[c + 1])], [False]])
+        edge = np.flatnonzero(m[1:] != m[:-1])
+        rows += [(c, int(a), int(b)) for a, b in zip(edge[0::2], edge[1::2])]
+    return rows
+
+
+def format_mask_rows(rows, contig_names):
+    """--dust-out: contig name, start, end (0-based, half-open), tab-separated."""
+    return ["{}\t{}\t{}".format(contig_names[c], a, b) for c, a, b in rows]
 
 
 # ---------------------------------------------------------------------------
@@ -279,14 +335,23 @@ def format_rows(rec, order, contig_names, contig_lens, subject_ids, subject_lens
 
 
 def search_files(query, db, out_path, device=0, chunk_bases=CHUNK_BASES, max_target_seqs=MAX_TARGET_SEQS,
-                 say=lambda *a: None, gapped=False, band=15, xdrop_gap=30, **params):
+                 say=lambda *a: None, gapped=False, band=15, xdrop_gap=30, dust=False, dust_window=64,
+                 dust_level=20, dust_out=None, **params):
     """The native search of the FASTA `db` against the contigs `query`, written to `out_path`;
-    gapped: the alignments of the gapped extension in place of the ungapped HSPs.
+    gapped: the alignments of the gapped extension in place of the ungapped HSPs; dust: seeds
+    from the contigs' unmasked S-mers only, and with dust_out the masked intervals written there.
     Returns the searcher's counters plus rows, subjects and database bases."""
     fields = GAP_RECORD_FIELDS if gapped else RECORD_FIELDS
     names, seq, off = mapper.read_fasta(query)
     ids, lens, parts = [], [], []
-    with Searcher(seq, off, device=device, band=band, xdrop_gap=xdrop_gap, **params) as s:
+    with Searcher(seq, off, device=device, band=band, xdrop_gap=xdrop_gap, dust=dust, dust_window=dust_window,
+                  dust_level=dust_level, **params) as s:
+        if dust:
+            say("  {:,} of {:,} contig bases masked; {:,} of {:,} seeds kept".format(
+                s.dust_stats["masked_bases"], len(seq), s.dust_stats["kmers_after"], s.dust_stats["kmers_before"]))
+            if dust_out:
+                with open(dust_out, "w") as fh:
+                    fh.write("".join(r + "\n" for r in format_mask_rows(mask_intervals(s.mask(), off), names)))
         for cid, cseq, coff in iter_subject_chunks(db, chunk_bases):
             rec = search_chunk(s, cseq, coff, gapped)
             rec["subject"] = rec["subject"] + np.int32(len(ids))
@@ -348,6 +413,17 @@ def build_parser():
                    help="--gapped: diagonals either way of the anchor's, per side")
     g.add_argument("--xdrop-gap", type=int, default=GAP_DEFAULTS["xdrop_gap"], metavar="<1..1000>",
                    help="--gapped: x-drop of the gapped extension, raw score")
+    g.add_argument("--dust", action="store_true",
+                   help="mask the contigs' low-complexity stretches (symmetric DUST, the published\n"
+                        "definition; agreement with NCBI dustmasker is not measured): they give no\n"
+                        "seeds, extensions still run through them.  blastn's default is on\n[default: off]")
+    g.add_argument("--dust-window", type=int, default=DUST_DEFAULTS["dust_window"], metavar="<8..64>",
+                   help="--dust: the longest interval scored, in bases")
+    g.add_argument("--dust-level", type=int, default=DUST_DEFAULTS["dust_level"], metavar="<int>",
+                   help="--dust: an interval is masked when its score exceeds level / 10")
+    g.add_argument("--dust-out", default=None, metavar="<path>",
+                   help="--dust: write the masked intervals there, one per line in FASTA order:\n"
+                        "contig name, start, end (0-based, half-open)")
     return ap
 
 
@@ -381,12 +457,15 @@ def main(argv=None):
         return
     if args.max_target_seqs < 1 or args.chunk_bases < 1:
         die("--max-target-seqs and --chunk-bases must be positive")
+    if args.dust_out and not args.dust:
+        die("--dust-out needs --dust")
     try:
         stats = search_files(args.query, args.db, args.out, device=args.gpu, chunk_bases=args.chunk_bases,
                              max_target_seqs=args.max_target_seqs, say=inputs.say,
                              seed_length=args.seed_length, seed_stride=args.seed_stride,
                              max_seed_hits=args.max_seed_hits, xdrop=args.xdrop, min_score=args.min_score,
-                             gapped=args.gapped, band=args.band, xdrop_gap=args.xdrop_gap)
+                             gapped=args.gapped, band=args.band, xdrop_gap=args.xdrop_gap, dust=args.dust,
+                             dust_window=args.dust_window, dust_level=args.dust_level, dust_out=args.dust_out)
     except (inputs.InputError, OSError, L.WaafleHipError) as exc:
         die(str(exc))
     inputs.say("Finished successfully ({:,} rows from {:,} subjects; {:,} seed hits).".format(
