@@ -36,7 +36,7 @@ def main():
         name = r["name"].replace("(anonymous namespace)::", "").replace("void ", "")
         name = re.sub(r"\(.*", "", name)
         print("{:48s} vgpr {:>4s} agpr {:>3s} sgpr {:>3s} spill {:>3s} scratch {:>4s} lds {:>6s} occ {:>2s}".format(
-            name[:48], r.get("VGPRs", "?"), r.get("AGPRs", "?"), r.get("SGPRs", "?"),
+            name[:48], r.get("VGPRs", "?"), r.get("AGPRs", "?"), r.get("TotalSGPRs", r.get("SGPRs", "?")),
             r.get("VGPRs Spill", "?"), r.get("ScratchSize [bytes/lane]", "?"),
             r.get("LDS Size [bytes/block]", "?"), r.get("Occupancy [waves/SIMD]", "?")))
 

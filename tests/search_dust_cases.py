@@ -79,8 +79,33 @@ def no_low_complexity():
     return contigs, subjects, params(), n, n
 
 
+STRADDLE_MASK = (160, 200)       # the masked bases of the straddle cases' contig
+
+
+def _straddle(S):
+    """One contig of 300 bases whose only masked bases are a poly-A x40 at 160..199, the start
+    of a 32-bit word of the mask plane.  q = 160 - (S - 1): the S-mer at q starts inside the
+    word before (q & 31 != 0) and its only masked base is its last one, the first of the next
+    word; the S-mer at q - 1 is unmasked.  Each is a subject of its own with the one seed at
+    a = 0 (min_score S, so the S-base HSP is reported): without the mask a record each, with
+    it only the S-mer at q - 1 is in the index."""
+    contig = _no_a(rnd(160, 230)) + "A" * 40 + _no_a(rnd(100, 231))
+    q = STRADDLE_MASK[0] - (S - 1)
+    return [contig], [contig[q - 1:q - 1 + S], contig[q:q + S]], params(S=S, min_score=S), 2, 1
+
+
+def straddle_s32():
+    """_straddle at the longest seed: q = 129, the window of 32 bases spans two whole words."""
+    return _straddle(32)
+
+
+def straddle_s12():
+    """_straddle at the shortest seed: q = 149, one base of the window in the next word."""
+    return _straddle(12)
+
+
 HAND_BUILT = {f.__name__: f for f in (poly_a_against_poly_a, internal_poly_a, trap, max_occ_interplay,
-                                      no_low_complexity)}
+                                      no_low_complexity, straddle_s32, straddle_s12)}
 
 
 def planted_gapped():

@@ -97,6 +97,25 @@ def test_masked_cases_show_what_they_claim():
     assert sdo.search_indexed(contigs, subjects, P) == so.search_indexed(contigs, subjects, P)
 
 
+@pytest.mark.parametrize("S", [32, 12])
+def test_straddle_cases_show_what_they_claim(S):
+    contigs, subjects, P, _, _ = sdc._straddle(S)
+    lo, hi = sdc.STRADDLE_MASK
+    mask = do.mask_windows(contigs)
+    assert (mask == do.mask_brute(contigs)).all()
+    assert len(contigs) == 1 and len(contigs[0]) == 300 and P["S"] == S
+    assert mask[lo:hi].all() and int(mask.sum()) == hi - lo      # the poly-A and nothing else
+    q = lo - (S - 1)
+    assert q & 31 != 0 and q >> 5 == (lo >> 5) - 1 and lo & 31 == 0
+    assert not mask[q - 1:q - 1 + S].any()                       # the S-mer at q - 1 is unmasked,
+    assert mask[q:q + S].tolist() == [False] * (S - 1) + [True]  # the one at q only in the next word
+    assert subjects == [contigs[0][q - 1:q - 1 + S], contigs[0][q:q + S]]
+    assert all(contigs[0].count(s) == 1 for s in subjects)
+    assert so.search_indexed(contigs, subjects, P) == [(0, 0, 0, q - 1, 0, S, S), (0, 1, 0, q, 0, S, S)]
+    assert sdo.search_indexed(contigs, subjects, P) == sdo.search_brute(contigs, subjects, P) == \
+        [(0, 0, 0, q - 1, 0, S, S)]
+
+
 def test_gapped_planted_gene_with_poly_a_is_one_alignment():
     contigs, subjects, P, n_plain, n_masked = sdc.planted_gapped()
     assert do.mask_windows(contigs)[1000:1030].all()

@@ -25,7 +25,7 @@
 //   belong to the next tile as well.
 // k_dust_count: the masked bases.
 // dust_mask then rebuilds the S-mer index without the S-mers that hold a masked base
-// (map_build_index, wf_map.hip).
+// (map_build_index, wf_map.hip: k_map_flag with the mask plane as its argument).
 #include <algorithm>
 #include <string>
 
@@ -130,39 +130,34 @@ int dust_mask(MapState* st, int window, int level, DustStats* stats, uint32_t* h
   const int64_t total = st->total;
   const int64_t words = (total + 31) / 32 + 2;
   const int Lv = std::min(level, 20000);                     // 10 r <= 18910: nothing passes; no overflow
-  MapBuf d_n;
-  unsigned long long masked = 0;
-  int rc = 0;
-  MAP_RC(map_ensure(st->dm, (size_t)words * sizeof(uint32_t), err));
-  MAP_RC(map_ensure(d_n, sizeof(unsigned long long), err));
-  MAP_TRY(hipMemsetAsync(st->dm.p, 0, (size_t)words * sizeof(uint32_t), s));
-  MAP_TRY(hipMemsetAsync(d_n.p, 0, sizeof(unsigned long long), s));
-  if (total > 0) {
-    MapIndexView ix = map_view(st);
-    hipLaunchKernelGGL(k_dust_mask, dim3((unsigned)((total + kDustTile - 1) / kDustTile)), dim3(kDustBlock), 0, s,
-                       ix, (int)total, window, Lv, static_cast<uint32_t*>(st->dm.p));
-    MAP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_dust_count, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, s,
-                       static_cast<const uint32_t*>(st->dm.p), words, static_cast<unsigned long long*>(d_n.p));
-    MAP_TRY(hipGetLastError());
-  }
-  MAP_TRY(hipMemcpyAsync(&masked, d_n.p, sizeof masked, hipMemcpyDeviceToHost, s));
-  if (host_mask && total > 0)
-    MAP_TRY(hipMemcpyAsync(host_mask, st->dm.p, (size_t)((total + 31) / 32) * sizeof(uint32_t),
-                           hipMemcpyDeviceToHost, s));
-  MAP_TRY(hipStreamSynchronize(s));
-  st->have_mask = false;                                     // until the index matches the mask
-  MAP_RC(map_build_index(st, static_cast<const uint32_t*>(st->dm.p), s, err));
-  st->have_mask = true;
-  stats->masked_bases = (int64_t)masked;
-  stats->kmers_before = st->n_kmers_plain;
-  stats->kmers_after = st->n_kmers;
-done:
-  if (rc) {
-    (void)hipStreamSynchronize(s);
-    st->have_index = false;                                  // the index may be half built
-  }
-  map_release(d_n);
+  DevArr<unsigned long long> d_n;
+  const int rc = synced_on_error(s, [&]() -> int {
+    unsigned long long masked = 0;
+    MAP_RC(st->dm.ensure(words, err));
+    MAP_RC(d_n.ensure(1, err));
+    MAP_TRY(hipMemsetAsync(st->dm.p, 0, (size_t)words * sizeof(uint32_t), s));
+    MAP_TRY(hipMemsetAsync(d_n.p, 0, sizeof(unsigned long long), s));
+    if (total > 0) {
+      hipLaunchKernelGGL(k_dust_mask, dim3((unsigned)((total + kDustTile - 1) / kDustTile)), dim3(kDustBlock), 0, s,
+                         map_view(st), (int)total, window, Lv, st->dm.p);
+      MAP_TRY(hipGetLastError());
+      hipLaunchKernelGGL(k_dust_count, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, s, st->dm.p, words, d_n.p);
+      MAP_TRY(hipGetLastError());
+    }
+    MAP_TRY(hipMemcpyAsync(&masked, d_n.p, sizeof masked, hipMemcpyDeviceToHost, s));
+    if (host_mask && total > 0)
+      MAP_TRY(hipMemcpyAsync(host_mask, st->dm.p, (size_t)((total + 31) / 32) * sizeof(uint32_t),
+                             hipMemcpyDeviceToHost, s));
+    MAP_TRY(hipStreamSynchronize(s));
+    st->have_mask = false;                                   // until the index matches the mask
+    MAP_RC(map_build_index(st, st->dm.p, s, err));
+    st->have_mask = true;
+    stats->masked_bases = (int64_t)masked;
+    stats->kmers_before = st->n_kmers_plain;
+    stats->kmers_after = st->n_kmers;
+    return 0;
+  });
+  if (rc) st->have_index = false;                            // the index may be half built
   return rc;
 }
 

@@ -6,8 +6,9 @@
 //   k_map_pack    thread per 32 bases: the contig store as two bit planes in one 64-bit word
 //                 (x: low bit, y: high bit of the base code A0 C1 G2 T3) and a 1-bit N plane;
 //                 the store is padded so the window read of words w and w + 1 stays in bounds
+//                 (map_pack; the homology search packs its chunks with it, in both orientations)
 //   k_map_flag    thread per position: 1 when the S-mer there has no N and stays in its contig
-//                 (k_map_flag_masked: and holds no base of the low-complexity mask, wf_dust.hip)
+//                 and, given the low-complexity mask (wf_dust.hip), holds no masked base
 //   k_map_emit    (device scan of the flags) -> compact (key, position) pairs, position order;
 //                 key = high-plane bits << S | low-plane bits
 //   device radix sort on the 2S key bits (stable: equal keys keep ascending positions)
@@ -43,7 +44,7 @@
 
 #include "wf_internal.h"
 #include "wf_lanes.h"
-#include "wf_mapstore.h"   // the store and index: MapState, MapIndexView, k_map_pack, the helpers
+#include "wf_mapstore.h"   // the shared layer: DevArr, MapState, MapIndexView, the device helpers
 
 namespace wf {
 
@@ -63,25 +64,26 @@ struct MapPairArgs {
   int32_t* contig; int32_t* pos1; int32_t* pos2; uint8_t* strand1; uint8_t* mm1; uint8_t* mm2;
 };
 
-__global__ void k_map_flag(const MapIndexView ix, int n_pos, int32_t* flag) {
-  const int q = blockIdx.x * blockDim.x + threadIdx.x;
-  if (q >= n_pos) return;
-  uint64_t key;
-  const int c = contig_of(ix.coff, ix.n_contigs, q);
-  flag[q] = (int64_t)q + ix.S <= ix.coff[c + 1] && store_kmer(ix, q, &key);
+// thread per word of the planes; rc: word w holds seq[total - 1 - 32 w] downwards, complemented
+__global__ void k_map_pack(const unsigned char* seq, int64_t total, int64_t words, bool rc, uint2* pk, uint32_t* nm) {
+  const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= words) return;
+  const int count = (int)std::min<int64_t>(std::max<int64_t>(total - w * 32, 0), 32);
+  const Planes32 v = pack32(rc ? seq + (total - 1 - w * 32) : seq + w * 32, rc ? -1 : 1, count, rc);
+  pk[w] = make_uint2(v.lo, v.hi);
+  nm[w] = v.n | (count < 32 ? ~0u << count : 0u);            // the padding is N
 }
 
-// k_map_flag for an index with a low-complexity mask (wf_search_mask): the S bases must be
-// unmasked in dm too.  A kernel of its own, so that the mapper's k_map_flag stays as it is.
-__global__ void k_map_flag_masked(const MapIndexView ix, const uint32_t* dm, int n_pos, int32_t* flag) {
+// dm null: the flags of the plain index; else the S bases must be unmasked in dm too.  The
+// windows are read before the contig is known (q < n_pos: inside the planes either way), so
+// that neither the loads nor the test of dm wait for the search of coff.
+__global__ void k_map_flag(const MapIndexView ix, const uint32_t* dm, int n_pos, int32_t* flag) {
   const int q = blockIdx.x * blockDim.x + threadIdx.x;
   if (q >= n_pos) return;
-  uint64_t key;
+  uint32_t bad = plane_window(ix.nm, q);                     // an N among the 32 bases from q on,
+  if (dm) bad |= plane_window(dm, q);                        //   or a masked base
   const int c = contig_of(ix.coff, ix.n_contigs, q);
-  const int W = q >> 5, sh = q & 31;
-  const uint32_t mask = ix.S == 32 ? 0xFFFFFFFFu : (1u << ix.S) - 1u;
-  flag[q] = (int64_t)q + ix.S <= ix.coff[c + 1] && store_kmer(ix, q, &key) &&
-            (window32(dm[W], dm[W + 1], sh) & mask) == 0;
+  flag[q] = (int64_t)q + ix.S <= ix.coff[c + 1] && (bad & smer_mask(ix.S)) == 0;
 }
 
 __global__ void k_map_emit(const MapIndexView ix, int n_pos, const int32_t* flag, const int32_t* slot,
@@ -89,7 +91,7 @@ __global__ void k_map_emit(const MapIndexView ix, int n_pos, const int32_t* flag
   const int q = blockIdx.x * blockDim.x + threadIdx.x;
   if (q >= n_pos || !flag[q]) return;
   uint64_t key = 0;
-  store_kmer(ix, q, &key);
+  planes_kmer(ix.pk, ix.nm, ix.S, q, &key);
   keys[slot[q]] = key;
   kpos[slot[q]] = q;
 }
@@ -120,19 +122,12 @@ __device__ __forceinline__ void map_pack_variants(const unsigned char* asc, int 
   const int v = lane >> 4, slot = lane & 15;
   const int Lv = (v >> 1) ? L2 : L1;
   const unsigned char* src = asc + (v >> 1) * kMapMaxRead;
-  uint32_t lo = 0, hi = 0, n = 0;
-  for (int b = 0; b < 32; ++b) {
-    const int i = slot * 32 + b;
-    if (i >= Lv) break;
-    int code = base_code((v & 1) ? src[Lv - 1 - i] : src[i]);
-    if ((v & 1) && code < 4) code = 3 - code;
-    lo |= (uint32_t)(code & 1) << b;
-    hi |= (uint32_t)((code >> 1) & 1) << b;
-    n |= (uint32_t)(code >> 2) << b;
-  }
-  xlo[v * kMapRow + slot] = lo & ~n;
-  xhi[v * kMapRow + slot] = hi & ~n;
-  xnn[v * kMapRow + slot] = n;
+  const bool rc = v & 1;
+  const Planes32 x = pack32(rc ? src + (Lv - 1 - slot * 32) : src + slot * 32, rc ? -1 : 1,
+                            min(max(Lv - slot * 32, 0), 32), rc);
+  xlo[v * kMapRow + slot] = x.lo;
+  xhi[v * kMapRow + slot] = x.hi;
+  xnn[v * kMapRow + slot] = x.n;
   if (slot == 0) {
     xlo[v * kMapRow + kMapWords] = 0;
     xhi[v * kMapRow + kMapWords] = 0;
@@ -150,21 +145,12 @@ __device__ __forceinline__ int map_seed_lookup(const MapIndexView& ix, int max_o
   const int off = slot * S;
   int cnt = 0;
   if (slot < min(Lv / S, kMapSlots)) {
-    const int W = off >> 5, sh = off & 31;
-    const uint32_t mask = S == 32 ? 0xFFFFFFFFu : (1u << S) - 1u;
-    const uint32_t* r = xnn + v * kMapRow + W;
-    if ((window32(r[0], r[1], sh) & mask) == 0) {
-      const uint32_t* pl = xlo + v * kMapRow + W;
-      const uint32_t* ph = xhi + v * kMapRow + W;
-      const uint64_t key = ((uint64_t)(window32(ph[0], ph[1], sh) & mask) << S) | (window32(pl[0], pl[1], sh) & mask);
-      const uint32_t b = (uint32_t)(key >> ix.bshift);
-      int lo = (int)ix.bucket[b];
-      const int end = (int)ix.bucket[b + 1];
-      int hi = end;
-      while (lo < hi) {                                      // lower bound within the bucket
-        const int mid = (lo + hi) >> 1;
-        if (ix.keys[mid] < key) lo = mid + 1; else hi = mid;
-      }
+    const uint32_t mask = smer_mask(S);
+    if ((plane_window(xnn + v * kMapRow, off) & mask) == 0) {
+      const uint64_t key = ((uint64_t)(plane_window(xhi + v * kMapRow, off) & mask) << S) |
+                           (plane_window(xlo + v * kMapRow, off) & mask);
+      int end;
+      const int lo = index_lower_bound(ix, key, &end);
       *first = lo;
       while (cnt <= max_occ && lo + cnt < end && ix.keys[lo + cnt] == key) ++cnt;
       if (cnt > max_occ) cnt = 0;
@@ -529,62 +515,72 @@ __global__ __launch_bounds__(64) void k_map_gap(const MapGapArgs G) {
 // device, then k_map_gap in launches of at most kMapGapLaunch pairs.
 int map_rescue(MapState* st, MapGapArgs GA, hipStream_t s, std::string* err) {
   const int64_t NP = GA.P.n_pairs;
-  int rc = 0;
-  int32_t last_flag = 0, last_slot = 0;
-  size_t tmp_bytes = 0;
-  int32_t *flag, *slot;
-  int64_t n = 0;
+  const unsigned blocks = (unsigned)((NP + 255) / 256);
   const size_t lds = (size_t)kMapGapFixedLds + (size_t)kMapGapEntryLds * 64 * (size_t)GA.P.max_occ;
-  MAP_RC(map_ensure(st->g_flag, sizeof(int32_t) * NP, err));
-  MAP_RC(map_ensure(st->g_slot, sizeof(int32_t) * NP, err));
-  MAP_RC(map_ensure(st->g_idx, sizeof(int32_t) * NP, err));
-  flag = static_cast<int32_t*>(st->g_flag.p);
-  slot = static_cast<int32_t*>(st->g_slot.p);
-  hipLaunchKernelGGL(k_map_gap_flag, dim3((unsigned)((NP + 255) / 256)), dim3(256), 0, s, GA.P, flag);
+  MAP_RC(st->g_flag.ensure(NP, err));
+  MAP_RC(st->g_slot.ensure(NP, err));
+  MAP_RC(st->g_idx.ensure(NP, err));
+  hipLaunchKernelGGL(k_map_gap_flag, dim3(blocks), dim3(256), 0, s, GA.P, st->g_flag.p);
   MAP_TRY(hipGetLastError());
-  MAP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, flag, slot, (int)NP, s));
-  MAP_RC(map_ensure(st->g_tmp, tmp_bytes, err));
-  MAP_TRY(hipcub::DeviceScan::ExclusiveSum(st->g_tmp.p, tmp_bytes, flag, slot, (int)NP, s));
-  hipLaunchKernelGGL(k_map_gap_list, dim3((unsigned)((NP + 255) / 256)), dim3(256), 0, s, NP, flag, slot,
-                     static_cast<int32_t*>(st->g_idx.p));
-  MAP_TRY(hipGetLastError());
-  MAP_TRY(hipMemcpyAsync(&last_flag, flag + (NP - 1), sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  MAP_TRY(hipMemcpyAsync(&last_slot, slot + (NP - 1), sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  MAP_TRY(hipStreamSynchronize(s));
-  n = (int64_t)last_flag + last_slot;
+  int64_t n = 0;
+  MAP_RC(scan_reserve(st->g_tmp, (int)NP, s, err));
+  MAP_RC(scan_total(st->g_flag.p, st->g_slot.p, (int)NP, st->g_tmp, &n, s, err));
   if (n == 0) return 0;
+  hipLaunchKernelGGL(k_map_gap_list, dim3(blocks), dim3(256), 0, s, NP, st->g_flag.p, st->g_slot.p, st->g_idx.p);
+  MAP_TRY(hipGetLastError());
   MAP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_map_gap),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   for (int64_t lo = 0; lo < n; lo += kMapGapLaunch) {
     GA.n = (int)std::min<int64_t>(kMapGapLaunch, n - lo);
-    GA.idx = static_cast<const int32_t*>(st->g_idx.p) + lo;
+    GA.idx = st->g_idx.p + lo;
     hipLaunchKernelGGL(k_map_gap, dim3((unsigned)GA.n), dim3(64), lds, s, GA);
     MAP_TRY(hipGetLastError());
   }
-done:
-  return rc;
+  return 0;
 }
 
 }  // namespace
 
 MapState* map_create() { return new MapState(); }
 
-void map_destroy(MapState* st) {
-  if (!st) return;
-  MapBuf* bufs[] = {&st->pk, &st->nm, &st->coff, &st->keys, &st->kpos, &st->bucket, &st->s1, &st->o1,
-                    &st->s2, &st->o2, &st->r_contig, &st->r_pos1, &st->r_pos2, &st->r_strand, &st->r_mm1,
-                    &st->r_mm2, &st->r_d1, &st->r_d2, &st->r_k1, &st->r_k2, &st->r_flags, &st->g_flag,
-                    &st->g_slot, &st->g_idx, &st->g_tmp, &st->dm};
-  for (MapBuf* b : bufs) map_release(*b);
-  search_destroy(st->search);
-  delete st;
-}
+void map_destroy(MapState* st) { delete st; }
 
 int map_index_params(const MapState* st, int* seed_len, int* max_occ) {
   if (!st || !st->have_index) return 0;
   *seed_len = st->seed_len;
   *max_occ = st->max_occ;
   return 1;
+}
+
+MapIndexView map_view(const MapState* st) {
+  return MapIndexView{st->pk.p, st->nm.p, st->coff.p, st->keys.p, st->kpos.p, st->bucket.p,
+                      st->n_contigs, st->seed_len, st->bshift, st->have_mask ? st->dm.p : nullptr};
+}
+
+int map_pack(const unsigned char* seq, int64_t total, bool rc, uint2* pk, uint32_t* nm, hipStream_t s,
+             std::string* err) {
+  const int64_t words = (total + 31) / 32 + 2;
+  hipLaunchKernelGGL(k_map_pack, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, s, seq, total, words, rc, pk, nm);
+  MAP_TRY(hipGetLastError());
+  return 0;
+}
+
+int scan_reserve(DevArr<unsigned char>& tmp, int n, hipStream_t s, std::string* err) {
+  size_t bytes = 0;
+  MAP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, (const int32_t*)nullptr, (int32_t*)nullptr, n, s));
+  return tmp.ensure(bytes, err);
+}
+
+int scan_total(const int32_t* flag, int32_t* slot, int n, const DevArr<unsigned char>& tmp, int64_t* sum,
+               hipStream_t s, std::string* err) {
+  size_t bytes = tmp.n * sizeof(unsigned char);              // all of the scratch: no less than n needs
+  MAP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp.p, bytes, flag, slot, n, s));
+  int32_t last_flag = 0, last_slot = 0;
+  MAP_TRY(hipMemcpyAsync(&last_flag, flag + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  MAP_TRY(hipMemcpyAsync(&last_slot, slot + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  MAP_TRY(hipStreamSynchronize(s));
+  *sum = (int64_t)last_flag + last_slot;
+  return 0;
 }
 
 int map_index(MapState* st, const char* seq, const int64_t* off, int n_contigs, int seed_len, int max_occ,
@@ -601,99 +597,74 @@ int map_index(MapState* st, const char* seq, const int64_t* off, int n_contigs, 
   std::vector<int32_t> coff((size_t)n_contigs + 1, 0);
   for (int c = 0; c <= n_contigs && n_contigs > 0; ++c) coff[c] = (int32_t)off[c];
   const int64_t words = (total + 31) / 32 + 2;
-  MapBuf d_seq;
-  int rc = 0;
-  MAP_RC(map_ensure(st->pk, (size_t)words * sizeof(uint2), err));
-  MAP_RC(map_ensure(st->nm, (size_t)words * sizeof(uint32_t), err));
-  MAP_RC(map_ensure(st->coff, coff.size() * sizeof(int32_t), err));
-  MAP_RC(map_ensure(d_seq, (size_t)total, err));
-  MAP_TRY(hipMemcpyAsync(st->coff.p, coff.data(), coff.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-  if (total > 0) MAP_TRY(hipMemcpyAsync(d_seq.p, seq, (size_t)total, hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(k_map_pack, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, s,
-                     static_cast<const unsigned char*>(d_seq.p), total, words, static_cast<uint2*>(st->pk.p),
-                     static_cast<uint32_t*>(st->nm.p));
-  MAP_TRY(hipGetLastError());
-  st->n_contigs = n_contigs;
-  st->seed_len = seed_len;
-  st->max_occ = max_occ;
-  st->total = total;
-  MAP_RC(map_build_index(st, nullptr, s, err));
-  st->n_kmers_plain = st->n_kmers;
-  st->have_index = true;
-done:
-  if (rc) (void)hipStreamSynchronize(s);
-  map_release(d_seq);
-  return rc;
+  DevArr<unsigned char> d_seq;
+  return synced_on_error(s, [&]() -> int {
+    MAP_RC(st->pk.ensure(words, err));
+    MAP_RC(st->nm.ensure(words, err));
+    MAP_RC(st->coff.ensure(coff.size(), err));
+    MAP_RC(d_seq.ensure(total, err));
+    MAP_TRY(hipMemcpyAsync(st->coff.p, coff.data(), coff.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (total > 0) MAP_TRY(hipMemcpyAsync(d_seq.p, seq, (size_t)total, hipMemcpyHostToDevice, s));
+    MAP_RC(map_pack(d_seq.p, total, false, st->pk.p, st->nm.p, s, err));
+    st->n_contigs = n_contigs;
+    st->seed_len = seed_len;
+    st->max_occ = max_occ;
+    st->total = total;
+    MAP_RC(map_build_index(st, nullptr, s, err));
+    st->n_kmers_plain = st->n_kmers;
+    st->have_index = true;
+    return 0;
+  });
 }
 
 int map_build_index(MapState* st, const uint32_t* dm, hipStream_t s, std::string* err) {
   const int seed_len = st->seed_len;
   const int n_pos = (int)std::max<int64_t>(st->total - seed_len + 1, 0);
-  MapBuf d_flag, d_slot, d_keys, d_kpos, d_tmp;
-  int rc = 0;
-  int32_t last_flag = 0, last_slot = 0;
-  int64_t nk = 0;
-  int bits = 0;
-  size_t tmp_bytes = 0;
-  const MapIndexView ix = map_view(st);
-  if (n_pos > 0) {
-    MAP_RC(map_ensure(d_flag, (size_t)n_pos * sizeof(int32_t), err));
-    MAP_RC(map_ensure(d_slot, (size_t)n_pos * sizeof(int32_t), err));
-    if (dm)
-      hipLaunchKernelGGL(k_map_flag_masked, dim3((unsigned)((n_pos + 255) / 256)), dim3(256), 0, s, ix, dm, n_pos,
-                         static_cast<int32_t*>(d_flag.p));
-    else
-      hipLaunchKernelGGL(k_map_flag, dim3((unsigned)((n_pos + 255) / 256)), dim3(256), 0, s, ix, n_pos,
-                         static_cast<int32_t*>(d_flag.p));
+  const unsigned blocks = (unsigned)((n_pos + 255) / 256);
+  // declared in the reverse of the order they are to be freed in (flag, slot, keys, kpos, tmp):
+  // the order decides which freed blocks the buffers allocated next reuse
+  DevArr<unsigned char> d_tmp;
+  DevArr<int32_t> d_kpos;
+  DevArr<uint64_t> d_keys;
+  DevArr<int32_t> d_slot, d_flag;
+  return synced_on_error(s, [&]() -> int {
+    const MapIndexView ix = map_view(st);
+    int64_t nk = 0;
+    if (n_pos > 0) {
+      MAP_RC(d_flag.ensure(n_pos, err));
+      MAP_RC(d_slot.ensure(n_pos, err));
+      hipLaunchKernelGGL(k_map_flag, dim3(blocks), dim3(256), 0, s, ix, dm, n_pos, d_flag.p);
+      MAP_TRY(hipGetLastError());
+      MAP_RC(scan_reserve(d_tmp, n_pos, s, err));
+      MAP_RC(scan_total(d_flag.p, d_slot.p, n_pos, d_tmp, &nk, s, err));
+    }
+    MAP_RC(st->keys.ensure(std::max<int64_t>(nk, 1), err));
+    MAP_RC(st->kpos.ensure(std::max<int64_t>(nk, 1), err));
+    if (nk > 0) {
+      MAP_RC(d_keys.ensure(nk, err));
+      MAP_RC(d_kpos.ensure(nk, err));
+      hipLaunchKernelGGL(k_map_emit, dim3(blocks), dim3(256), 0, s, ix, n_pos, d_flag.p, d_slot.p, d_keys.p, d_kpos.p);
+      MAP_TRY(hipGetLastError());
+      size_t bytes = 0;
+      MAP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, d_keys.p, st->keys.p, d_kpos.p, st->kpos.p, (int)nk, 0,
+                                                 2 * seed_len, s));
+      MAP_RC(d_tmp.ensure(bytes, err));
+      MAP_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, bytes, d_keys.p, st->keys.p, d_kpos.p, st->kpos.p, (int)nk, 0,
+                                                 2 * seed_len, s));
+    }
+    // table bits: about two buckets per S-mer, at least 2^8 and at most 2^26 entries
+    int bits = 8;
+    while (bits < 26 && ((int64_t)1 << bits) < 2 * nk) ++bits;
+    bits = std::min(bits, 2 * seed_len);
+    st->bshift = 2 * seed_len - bits;
+    st->n_kmers = nk;
+    MAP_RC(st->bucket.ensure(((size_t)1 << bits) + 1, err));
+    hipLaunchKernelGGL(k_map_bucket, dim3((unsigned)((nk + 1 + 255) / 256)), dim3(256), 0, s, st->keys.p, (int)nk,
+                       st->bshift, (uint32_t)1 << bits, st->bucket.p);
     MAP_TRY(hipGetLastError());
-    MAP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, static_cast<const int32_t*>(d_flag.p),
-                                             static_cast<int32_t*>(d_slot.p), n_pos, s));
-    MAP_RC(map_ensure(d_tmp, tmp_bytes, err));
-    MAP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, static_cast<const int32_t*>(d_flag.p),
-                                             static_cast<int32_t*>(d_slot.p), n_pos, s));
-    MAP_TRY(hipMemcpyAsync(&last_flag, static_cast<const int32_t*>(d_flag.p) + (n_pos - 1), sizeof(int32_t),
-                           hipMemcpyDeviceToHost, s));
-    MAP_TRY(hipMemcpyAsync(&last_slot, static_cast<const int32_t*>(d_slot.p) + (n_pos - 1), sizeof(int32_t),
-                           hipMemcpyDeviceToHost, s));
     MAP_TRY(hipStreamSynchronize(s));
-    nk = (int64_t)last_flag + last_slot;
-  }
-  MAP_RC(map_ensure(st->keys, (size_t)std::max<int64_t>(nk, 1) * sizeof(uint64_t), err));
-  MAP_RC(map_ensure(st->kpos, (size_t)std::max<int64_t>(nk, 1) * sizeof(int32_t), err));
-  if (nk > 0) {
-    MAP_RC(map_ensure(d_keys, (size_t)nk * sizeof(uint64_t), err));
-    MAP_RC(map_ensure(d_kpos, (size_t)nk * sizeof(int32_t), err));
-    hipLaunchKernelGGL(k_map_emit, dim3((unsigned)((n_pos + 255) / 256)), dim3(256), 0, s, ix, n_pos,
-                       static_cast<const int32_t*>(d_flag.p), static_cast<const int32_t*>(d_slot.p),
-                       static_cast<uint64_t*>(d_keys.p), static_cast<int32_t*>(d_kpos.p));
-    MAP_TRY(hipGetLastError());
-    tmp_bytes = 0;
-    MAP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, static_cast<const uint64_t*>(d_keys.p),
-                                               static_cast<uint64_t*>(st->keys.p),
-                                               static_cast<const int32_t*>(d_kpos.p),
-                                               static_cast<int32_t*>(st->kpos.p), (int)nk, 0, 2 * seed_len, s));
-    MAP_RC(map_ensure(d_tmp, tmp_bytes, err));
-    MAP_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, tmp_bytes, static_cast<const uint64_t*>(d_keys.p),
-                                               static_cast<uint64_t*>(st->keys.p),
-                                               static_cast<const int32_t*>(d_kpos.p),
-                                               static_cast<int32_t*>(st->kpos.p), (int)nk, 0, 2 * seed_len, s));
-  }
-  // table bits: about two buckets per S-mer, at least 2^8 and at most 2^26 entries
-  bits = 8;
-  while (bits < 26 && ((int64_t)1 << bits) < 2 * nk) ++bits;
-  bits = std::min(bits, 2 * seed_len);
-  st->bshift = 2 * seed_len - bits;
-  st->n_kmers = nk;
-  MAP_RC(map_ensure(st->bucket, (((size_t)1 << bits) + 1) * sizeof(uint32_t), err));
-  hipLaunchKernelGGL(k_map_bucket, dim3((unsigned)((nk + 1 + 255) / 256)), dim3(256), 0, s,
-                     static_cast<const uint64_t*>(st->keys.p), (int)nk, st->bshift, (uint32_t)1 << bits,
-                     static_cast<uint32_t*>(st->bucket.p));
-  MAP_TRY(hipGetLastError());
-  MAP_TRY(hipStreamSynchronize(s));
-done:
-  if (rc) (void)hipStreamSynchronize(s);
-  for (MapBuf* b : {&d_flag, &d_slot, &d_keys, &d_kpos, &d_tmp}) map_release(*b);
-  return rc;
+    return 0;
+  });
 }
 
 namespace {
@@ -702,12 +673,8 @@ namespace {
 int map_pairs_run(MapState* st, const MapReads& rd, const MapRule& rule, const MapOut& out, int max_gap,
                   const MapGapOut* gout, hipStream_t s, std::string* err) {
   const int64_t NP = rd.n_pairs;
-  MapGapArgs GA{};
-  int rc = 0;
   std::vector<int64_t> h1, h2;
   const int64_t *o1 = rd.off1, *o2 = rd.off2;
-  MapPairArgs A{};
-  size_t lds = 0;
   if (NP == 0) return 0;
   if (rd.device_resident) {      // the read lengths are checked on the host either way
     h1.resize(NP + 1);
@@ -730,6 +697,7 @@ int map_pairs_run(MapState* st, const MapReads& rd, const MapRule& rule, const M
       }
     }
   }
+  MapPairArgs A{};
   A.ix = map_view(st);
   A.max_occ = rule.max_occ;
   A.max_mm = rule.max_mm;
@@ -741,45 +709,38 @@ int map_pairs_run(MapState* st, const MapReads& rd, const MapRule& rule, const M
     A.contig = out.contig; A.pos1 = out.pos1; A.pos2 = out.pos2;
     A.strand1 = out.strand1; A.mm1 = out.mm1; A.mm2 = out.mm2;
   } else {
-    MAP_RC(map_ensure(st->s1, (size_t)o1[NP], err));
-    MAP_RC(map_ensure(st->s2, (size_t)o2[NP], err));
-    MAP_RC(map_ensure(st->o1, sizeof(int64_t) * (NP + 1), err));
-    MAP_RC(map_ensure(st->o2, sizeof(int64_t) * (NP + 1), err));
-    MAP_RC(map_ensure(st->r_contig, sizeof(int32_t) * NP, err));
-    MAP_RC(map_ensure(st->r_pos1, sizeof(int32_t) * NP, err));
-    MAP_RC(map_ensure(st->r_pos2, sizeof(int32_t) * NP, err));
-    MAP_RC(map_ensure(st->r_strand, (size_t)NP, err));
-    MAP_RC(map_ensure(st->r_mm1, (size_t)NP, err));
-    MAP_RC(map_ensure(st->r_mm2, (size_t)NP, err));
+    MAP_RC(st->s1.ensure(o1[NP], err));
+    MAP_RC(st->s2.ensure(o2[NP], err));
+    MAP_RC(st->o1.ensure(NP + 1, err));
+    MAP_RC(st->o2.ensure(NP + 1, err));
+    for (DevArr<int32_t>* b : {&st->r_contig, &st->r_pos1, &st->r_pos2}) MAP_RC(b->ensure(NP, err));
+    for (DevArr<uint8_t>* b : {&st->r_strand, &st->r_mm1, &st->r_mm2}) MAP_RC(b->ensure(NP, err));
     if (o1[NP] > 0) MAP_TRY(hipMemcpyAsync(st->s1.p, rd.seq1, (size_t)o1[NP], hipMemcpyHostToDevice, s));
     if (o2[NP] > 0) MAP_TRY(hipMemcpyAsync(st->s2.p, rd.seq2, (size_t)o2[NP], hipMemcpyHostToDevice, s));
     MAP_TRY(hipMemcpyAsync(st->o1.p, o1, sizeof(int64_t) * (NP + 1), hipMemcpyHostToDevice, s));
     MAP_TRY(hipMemcpyAsync(st->o2.p, o2, sizeof(int64_t) * (NP + 1), hipMemcpyHostToDevice, s));
-    A.s1 = static_cast<const char*>(st->s1.p); A.o1 = static_cast<const int64_t*>(st->o1.p);
-    A.s2 = static_cast<const char*>(st->s2.p); A.o2 = static_cast<const int64_t*>(st->o2.p);
-    A.contig = static_cast<int32_t*>(st->r_contig.p); A.pos1 = static_cast<int32_t*>(st->r_pos1.p);
-    A.pos2 = static_cast<int32_t*>(st->r_pos2.p); A.strand1 = static_cast<uint8_t*>(st->r_strand.p);
-    A.mm1 = static_cast<uint8_t*>(st->r_mm1.p); A.mm2 = static_cast<uint8_t*>(st->r_mm2.p);
+    A.s1 = st->s1.p; A.o1 = st->o1.p; A.s2 = st->s2.p; A.o2 = st->o2.p;
+    A.contig = st->r_contig.p; A.pos1 = st->r_pos1.p; A.pos2 = st->r_pos2.p;
+    A.strand1 = st->r_strand.p; A.mm1 = st->r_mm1.p; A.mm2 = st->r_mm2.p;
   }
-  lds = (size_t)kMapFixedLds + (size_t)16 * 64 * (size_t)rule.max_occ;
+  const size_t lds = (size_t)kMapFixedLds + (size_t)16 * 64 * (size_t)rule.max_occ;
   MAP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_map_pairs),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(k_map_pairs, dim3((unsigned)NP), dim3(64), lds, s, A);
   MAP_TRY(hipGetLastError());
+  MapGapArgs GA{};
   if (gout) {
     GA.P = A;
     GA.max_gap = max_gap;
     if (rd.device_resident) {
       GA.d1 = gout->d1; GA.d2 = gout->d2; GA.k1 = gout->k1; GA.k2 = gout->k2; GA.flags = gout->flags;
     } else {
-      MAP_RC(map_ensure(st->r_d1, (size_t)NP, err));
-      MAP_RC(map_ensure(st->r_d2, (size_t)NP, err));
-      MAP_RC(map_ensure(st->r_k1, sizeof(int16_t) * NP, err));
-      MAP_RC(map_ensure(st->r_k2, sizeof(int16_t) * NP, err));
-      MAP_RC(map_ensure(st->r_flags, (size_t)NP, err));
-      GA.d1 = static_cast<int8_t*>(st->r_d1.p); GA.d2 = static_cast<int8_t*>(st->r_d2.p);
-      GA.k1 = static_cast<int16_t*>(st->r_k1.p); GA.k2 = static_cast<int16_t*>(st->r_k2.p);
-      GA.flags = static_cast<uint8_t*>(st->r_flags.p);
+      MAP_RC(st->r_d1.ensure(NP, err));
+      MAP_RC(st->r_d2.ensure(NP, err));
+      MAP_RC(st->r_k1.ensure(NP, err));
+      MAP_RC(st->r_k2.ensure(NP, err));
+      MAP_RC(st->r_flags.ensure(NP, err));
+      GA.d1 = st->r_d1.p; GA.d2 = st->r_d2.p; GA.k1 = st->r_k1.p; GA.k2 = st->r_k2.p; GA.flags = st->r_flags.p;
     }
     MAP_TRY(hipMemsetAsync(GA.d1, 0, (size_t)NP, s));
     MAP_TRY(hipMemsetAsync(GA.d2, 0, (size_t)NP, s));
@@ -806,8 +767,7 @@ int map_pairs_run(MapState* st, const MapReads& rd, const MapRule& rule, const M
   } else if (gout) {
     MAP_TRY(hipStreamSynchronize(s));
   }
-done:
-  return rc;
+  return 0;
 }
 
 }  // namespace

@@ -5,7 +5,7 @@
 // (wf_dust.hip), which takes the low-complexity S-mers out of the index.
 //
 // One chunk (search_run):
-//   k_map_pack / k_search_pack_rc  the chunk as bit planes (wf_mapstore.h) in both orientations:
+//   map_pack twice   (k_map_pack, wf_map.hip) the chunk as bit planes in both orientations:
 //                    the minus store is the reverse complement of the whole chunk, so subject
 //                    [o, o') lies at [total - o', total - o) in it, reverse-complemented
 //   then, per tile of at most kSearchTile seed slots (slot = strand, subject, offset a = kT):
@@ -21,8 +21,6 @@
 //                    (a - T, same diagonal) is a seed hit too gives the same HSP and is skipped.
 //   The HSPs go to the host, which sorts them per (subject, strand, contig, diagonal), counts
 //   identical ones once, drops the strictly contained and those below min_score.
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 #include <string>
 #include <tuple>
@@ -30,25 +28,8 @@
 
 #include "wf_internal.h"
 #include "wf_mapstore.h"
-#include "wf_searchstate.h"
 
 namespace wf {
-
-struct SearchRaw {            // one extended seed hit
-  int32_t sm;                 // subject << 1 | minus
-  int32_t contig;
-  int32_t delta;              // contig position - variant position
-  int32_t b, e;               // [b, e) on the variant
-  int32_t score;
-};
-
-void search_destroy(SearchState* ss) {
-  if (!ss) return;
-  MapBuf* bufs[] = {&ss->seq, &ss->off, &ss->soff, &ss->pk[0], &ss->pk[1], &ss->nm[0], &ss->nm[1],
-                    &ss->cnt, &ss->first, &ss->start, &ss->tmp, &ss->raw, &ss->ctr, &ss->g_anchor, &ss->g_out};
-  for (MapBuf* b : bufs) map_release(*b);
-  delete ss;
-}
 
 namespace {
 
@@ -58,13 +39,11 @@ constexpr int64_t kSearchTileHits = 1 << 30;    //   slots * max_occ: the scan s
 
 struct SearchArgs {
   MapIndexView ix;            // the contigs
-  const uint2* vpk[2];        // the chunk: plus store, minus store
-  const uint32_t* vnm[2];
-  const int64_t* off;         // [n + 1] the subjects' starts in the chunk
+  ChunkView ch;               // the chunk
   const int64_t* soff;        // [n + 1] first seed slot of each subject (of one strand)
   int n_subjects;
   int T, max_occ, X;
-  int64_t NS, total;          // seed slots of one strand; bases of the chunk
+  int64_t NS;                 // seed slots of one strand
   int64_t t0;                 // the tile: slots [t0, t0 + nt) of the 2 NS
   int nt;
   int32_t* cnt;               // [nt]
@@ -90,48 +69,20 @@ __device__ __forceinline__ SearchSeed search_seed(const SearchArgs& A, int64_t t
   }
   sd.g = lo;
   sd.a = (int)(s - A.soff[lo]) * A.T;
-  const int64_t o0 = A.off[lo], o1 = A.off[lo + 1];
-  sd.M = (int)(o1 - o0);
-  sd.vbase = (int)(sd.strand ? A.total - o1 : o0);
+  chunk_place(A.ch, lo, sd.strand, &sd.M, &sd.vbase);
   return sd;
-}
-
-__global__ void k_search_pack_rc(const unsigned char* seq, int64_t total, int64_t words, uint2* pk, uint32_t* nm) {
-  const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (w >= words) return;
-  uint32_t lo = 0, hi = 0, n = 0;
-  for (int b = 0; b < 32; ++b) {
-    const int64_t i = w * 32 + b;
-    int code = i < total ? base_code(seq[total - 1 - i]) : 4;   // the padding is N
-    if (code < 4) code = 3 - code;
-    lo |= (uint32_t)(code & 1) << b;
-    hi |= (uint32_t)((code >> 1) & 1) << b;
-    n |= (uint32_t)(code >> 2) << b;
-  }
-  pk[w] = make_uint2(lo & ~n, hi & ~n);
-  nm[w] = n;
 }
 
 __global__ __launch_bounds__(256) void k_search_count(const SearchArgs A) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= A.nt) return;
   const SearchSeed sd = search_seed(A, A.t0 + j);
-  MapIndexView v = A.ix;                         // store_kmer on the chunk's planes
-  v.pk = A.vpk[sd.strand];
-  v.nm = A.vnm[sd.strand];
   uint64_t key = 0;
   int cnt = 0, first = 0;
-  if (store_kmer(v, sd.vbase + sd.a, &key)) {    // a + S <= M: words W, W + 1 are in the store
-    const uint32_t b = (uint32_t)(key >> A.ix.bshift);
-    int lo = (int)A.ix.bucket[b];
-    const int end = (int)A.ix.bucket[b + 1];
-    int hi = end;
-    while (lo < hi) {                            // lower bound within the bucket
-      const int mid = (lo + hi) >> 1;
-      if (A.ix.keys[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    first = lo;
-    hi = end;
+  // a + S <= M: words W, W + 1 are in the chunk's store
+  if (planes_kmer(A.ch.vpk[sd.strand], A.ch.vnm[sd.strand], A.ix.S, sd.vbase + sd.a, &key)) {
+    int hi;
+    int lo = first = index_lower_bound(A.ix, key, &hi);
     while (lo < hi) {                            // upper bound
       const int mid = (lo + hi) >> 1;
       if (A.ix.keys[mid] <= key) lo = mid + 1; else hi = mid;
@@ -141,23 +92,6 @@ __global__ __launch_bounds__(256) void k_search_count(const SearchArgs A) {
   }
   A.cnt[j] = cnt;
   A.first[j] = first;
-}
-
-// mismatch bits of the 32 columns whose first lies at position vp of the variant store and gp
-// of the contig store; either may be as low as -32 (the bases before a store are N)
-__device__ __forceinline__ uint32_t search_mis(const SearchArgs& A, int strand, int vp, int gp) {
-  const uint2* pk = A.vpk[strand];
-  const uint32_t* nm = A.vnm[strand];
-  const int W = vp >> 5, sh = vp & 31;
-  uint2 a = make_uint2(0u, 0u);
-  uint32_t na = ~0u;
-  if (W >= 0) {
-    a = pk[W];
-    na = nm[W];
-  }
-  const uint2 b = pk[W + 1];
-  const uint32_t vlo = window32(a.x, b.x, sh), vhi = window32(a.y, b.y, sh), vn = window32(na, nm[W + 1], sh);
-  return map_mis_word<true>(A.ix, &vlo, &vhi, &vn, 0, gp);
 }
 
 // The x-drop walk over the n columns of one word, bit k of m: the k-th column walked is a
@@ -208,13 +142,9 @@ __global__ __launch_bounds__(256) void k_search_extend(const SearchArgs A) {
   // low-complexity mask the index lacks the occurrences that hold a masked base, so the
   // occurrence at q - T counts only when its S bases are unmasked.
   if (sd.a >= T && j > 0 && A.cnt[j - 1] > 0 && q - T >= c0) {
-    uint32_t mis = search_mis(A, sd.strand, sd.vbase + sd.a - T, q - T);
+    uint32_t mis = chunk_mis(ix, A.ch, sd.strand, sd.vbase + sd.a - T, q - T);
     if (T < 32) mis &= (1u << T) - 1u;
-    if (ix.dm) {                                 // q - T >= 0; words W, W + 1 are in the plane
-      const int W = (q - T) >> 5, sh = (q - T) & 31;
-      const uint32_t smask = S == 32 ? 0xFFFFFFFFu : (1u << S) - 1u;
-      mis |= window32(ix.dm[W], ix.dm[W + 1], sh) & smask;
-    }
+    if (ix.dm) mis |= plane_window(ix.dm, q - T) & smer_mask(S);   // q - T >= 0: inside the plane
     if (mis == 0) {
       atomicAdd(&A.ctr[1], 1ull);
       return;
@@ -224,7 +154,7 @@ __global__ __launch_bounds__(256) void k_search_extend(const SearchArgs A) {
   int r = 0, best_r = 0, ext_r = 0;
   for (int i = sd.a + S, cols = 0; i < iend;) {
     const int n = min(32, iend - i);
-    const uint32_t mis = search_mis(A, sd.strand, sd.vbase + i, D + i);
+    const uint32_t mis = chunk_mis(ix, A.ch, sd.strand, sd.vbase + i, D + i);
     if (!search_walk(mis, n, A.X, cols, r, best_r, ext_r)) break;
     i += n;
     cols += n;
@@ -233,7 +163,7 @@ __global__ __launch_bounds__(256) void k_search_extend(const SearchArgs A) {
   r = 0;
   for (int i = sd.a - 1, cols = 0; i >= ibeg;) {
     const int n = min(32, i - ibeg + 1);
-    const uint32_t mis = __brev(search_mis(A, sd.strand, sd.vbase + i - 31, D + i - 31));
+    const uint32_t mis = __brev(chunk_mis(ix, A.ch, sd.strand, sd.vbase + i - 31, D + i - 31));
     if (!search_walk(mis, n, A.X, cols, r, best_l, ext_l)) break;
     i -= n;
     cols += n;
@@ -248,22 +178,10 @@ __global__ __launch_bounds__(256) void k_search_extend(const SearchArgs A) {
   A.raw[atomicAdd(&A.ctr[0], 1ull)] = out;       // at most nh <= kSearchLaunch per launch
 }
 
-#define SEARCH_TRY(x)                                                                     \
-  do {                                                                                    \
-    hipError_t e_ = (x);                                                                  \
-    if (e_ != hipSuccess) { *err = std::string(#x) + ": " + hipGetErrorString(e_); return -2; } \
-  } while (0)
-#define SEARCH_RC(x)                 \
-  do {                               \
-    const int rc_ = (x);             \
-    if (rc_) return rc_;             \
-  } while (0)
-
 // the seed hits of the chunk, extended: appended to *raw
 int search_device(MapState* st, const char* seq, const int64_t* off, int64_t n, const SearchRule& rule,
                   std::vector<SearchRaw>* raw, SearchStats* stats, hipStream_t s, std::string* err) {
-  if (!st->search) st->search = new SearchState();
-  SearchState* ss = st->search;
+  SearchState* ss = &st->search;
   const int64_t total = off[n];
   const int S = st->seed_len;
   std::vector<int64_t> soff((size_t)n + 1, 0);
@@ -274,67 +192,47 @@ int search_device(MapState* st, const char* seq, const int64_t* off, int64_t n, 
   const int64_t NS = soff[n];
   if (NS == 0) return 0;
   const int64_t words = (total + 31) / 32 + 2;
-  SEARCH_RC(map_ensure(ss->seq, (size_t)total, err));
-  SEARCH_RC(map_ensure(ss->off, sizeof(int64_t) * (n + 1), err));
-  SEARCH_RC(map_ensure(ss->soff, sizeof(int64_t) * (n + 1), err));
-  for (int v = 0; v < 2; ++v) {
-    SEARCH_RC(map_ensure(ss->pk[v], (size_t)words * sizeof(uint2), err));
-    SEARCH_RC(map_ensure(ss->nm[v], (size_t)words * sizeof(uint32_t), err));
-  }
   const int tile = (int)std::min<int64_t>(kSearchTile, kSearchTileHits / rule.max_occ);
   const int64_t tile_cap = std::min<int64_t>(tile, 2 * NS);
-  SEARCH_RC(map_ensure(ss->cnt, sizeof(int32_t) * tile_cap, err));
-  SEARCH_RC(map_ensure(ss->first, sizeof(int32_t) * tile_cap, err));
-  SEARCH_RC(map_ensure(ss->start, sizeof(int32_t) * tile_cap, err));
-  SEARCH_RC(map_ensure(ss->raw, sizeof(SearchRaw) * kSearchLaunch, err));
-  SEARCH_RC(map_ensure(ss->ctr, 2 * sizeof(unsigned long long), err));
-  SEARCH_TRY(hipMemcpyAsync(ss->seq.p, seq, (size_t)total, hipMemcpyHostToDevice, s));
-  SEARCH_TRY(hipMemcpyAsync(ss->off.p, off, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, s));
-  SEARCH_TRY(hipMemcpyAsync(ss->soff.p, soff.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, s));
-  const unsigned pack_blocks = (unsigned)((words + 255) / 256);
-  hipLaunchKernelGGL(k_map_pack, dim3(pack_blocks), dim3(256), 0, s, static_cast<const unsigned char*>(ss->seq.p),
-                     total, words, static_cast<uint2*>(ss->pk[0].p), static_cast<uint32_t*>(ss->nm[0].p));
-  SEARCH_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_search_pack_rc, dim3(pack_blocks), dim3(256), 0, s,
-                     static_cast<const unsigned char*>(ss->seq.p), total, words, static_cast<uint2*>(ss->pk[1].p),
-                     static_cast<uint32_t*>(ss->nm[1].p));
-  SEARCH_TRY(hipGetLastError());
+  MAP_RC(ss->seq.ensure(total, err));
+  MAP_RC(ss->off.ensure(n + 1, err));
+  MAP_RC(ss->soff.ensure(n + 1, err));
+  for (int v = 0; v < 2; ++v) {
+    MAP_RC(ss->pk[v].ensure(words, err));
+    MAP_RC(ss->nm[v].ensure(words, err));
+  }
+  MAP_RC(ss->cnt.ensure(tile_cap, err));
+  MAP_RC(ss->first.ensure(tile_cap, err));
+  MAP_RC(ss->start.ensure(tile_cap, err));
+  MAP_RC(ss->raw.ensure(kSearchLaunch, err));
+  MAP_RC(ss->ctr.ensure(2, err));
+  MAP_RC(scan_reserve(ss->tmp, (int)tile_cap, s, err));      // the largest tile: the loop allocates nothing
+  MAP_TRY(hipMemcpyAsync(ss->seq.p, seq, (size_t)total, hipMemcpyHostToDevice, s));
+  MAP_TRY(hipMemcpyAsync(ss->off.p, off, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, s));
+  MAP_TRY(hipMemcpyAsync(ss->soff.p, soff.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, s));
+  for (int v = 0; v < 2; ++v) MAP_RC(map_pack(ss->seq.p, total, v == 1, ss->pk[v].p, ss->nm[v].p, s, err));
 
   SearchArgs A{};
   A.ix = map_view(st);
-  for (int v = 0; v < 2; ++v) {
-    A.vpk[v] = static_cast<const uint2*>(ss->pk[v].p);
-    A.vnm[v] = static_cast<const uint32_t*>(ss->nm[v].p);
-  }
-  A.off = static_cast<const int64_t*>(ss->off.p);
-  A.soff = static_cast<const int64_t*>(ss->soff.p);
+  A.ch = chunk_view(*ss, total);
+  A.soff = ss->soff.p;
   A.n_subjects = (int)n;
   A.T = rule.stride;
   A.max_occ = rule.max_occ;
   A.X = rule.xdrop;
   A.NS = NS;
-  A.total = total;
-  A.cnt = static_cast<int32_t*>(ss->cnt.p);
-  A.first = static_cast<int32_t*>(ss->first.p);
-  A.start = static_cast<const int32_t*>(ss->start.p);
-  A.raw = static_cast<SearchRaw*>(ss->raw.p);
-  A.ctr = static_cast<unsigned long long*>(ss->ctr.p);
-  size_t tmp_bytes = 0;
-  SEARCH_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, A.cnt, static_cast<int32_t*>(ss->start.p),
-                                              (int)tile_cap, s));
-  SEARCH_RC(map_ensure(ss->tmp, tmp_bytes, err));
+  A.cnt = ss->cnt.p;
+  A.first = ss->first.p;
+  A.start = ss->start.p;
+  A.raw = ss->raw.p;
+  A.ctr = ss->ctr.p;
   for (int64_t t0 = 0; t0 < 2 * NS; t0 += tile) {
     A.t0 = t0;
     A.nt = (int)std::min<int64_t>(tile, 2 * NS - t0);
     hipLaunchKernelGGL(k_search_count, dim3((unsigned)((A.nt + 255) / 256)), dim3(256), 0, s, A);
-    SEARCH_TRY(hipGetLastError());
-    size_t tb = ss->tmp.bytes;
-    SEARCH_TRY(hipcub::DeviceScan::ExclusiveSum(ss->tmp.p, tb, A.cnt, static_cast<int32_t*>(ss->start.p), A.nt, s));
-    int32_t last_cnt = 0, last_start = 0;
-    SEARCH_TRY(hipMemcpyAsync(&last_cnt, A.cnt + (A.nt - 1), sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    SEARCH_TRY(hipMemcpyAsync(&last_start, A.start + (A.nt - 1), sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    SEARCH_TRY(hipStreamSynchronize(s));
-    const int64_t hits = (int64_t)last_cnt + last_start;
+    MAP_TRY(hipGetLastError());
+    int64_t hits = 0;
+    MAP_RC(scan_total(ss->cnt.p, ss->start.p, A.nt, ss->tmp, &hits, s, err));
     stats->seed_hits += hits;
     if (stats->seed_hits > 0x7FFFFFFFll) {
       *err = "more than 2^31 - 1 seed hits in one chunk";
@@ -344,21 +242,25 @@ int search_device(MapState* st, const char* seq, const int64_t* off, int64_t n, 
       A.h0 = (int)h0;
       A.nh = (int)std::min<int64_t>(kSearchLaunch, hits - h0);
       unsigned long long ctr[2] = {0, 0};
-      SEARCH_TRY(hipMemsetAsync(ss->ctr.p, 0, sizeof ctr, s));
+      MAP_TRY(hipMemsetAsync(ss->ctr.p, 0, sizeof ctr, s));
       hipLaunchKernelGGL(k_search_extend, dim3((unsigned)((A.nh + 255) / 256)), dim3(256), 0, s, A);
-      SEARCH_TRY(hipGetLastError());
-      SEARCH_TRY(hipMemcpyAsync(ctr, ss->ctr.p, sizeof ctr, hipMemcpyDeviceToHost, s));
-      SEARCH_TRY(hipStreamSynchronize(s));
+      MAP_TRY(hipGetLastError());
+      MAP_TRY(hipMemcpyAsync(ctr, ss->ctr.p, sizeof ctr, hipMemcpyDeviceToHost, s));
+      MAP_TRY(hipStreamSynchronize(s));
       stats->skipped += (int64_t)ctr[1];
       const size_t had = raw->size(), got = (size_t)std::min<unsigned long long>(ctr[0], kSearchLaunch);
       raw->resize(had + got);
-      if (got) SEARCH_TRY(hipMemcpy(raw->data() + had, ss->raw.p, got * sizeof(SearchRaw), hipMemcpyDeviceToHost));
+      if (got) MAP_TRY(hipMemcpy(raw->data() + had, ss->raw.p, got * sizeof(SearchRaw), hipMemcpyDeviceToHost));
     }
   }
   return 0;
 }
 
 }  // namespace
+
+ChunkView chunk_view(const SearchState& ss, int64_t total) {
+  return ChunkView{{ss.pk[0].p, ss.pk[1].p}, {ss.nm[0].p, ss.nm[1].p}, ss.off.p, total};
+}
 
 int search_records(MapState* st, const char* seq, const int64_t* off, int64_t n_subjects, const SearchRule& rule,
                    std::vector<SearchRec>* recs_out, SearchStats* stats, hipStream_t s, std::string* err) {

@@ -11,8 +11,8 @@
 //   predecessors, fetched with __shfl_down / __shfl_up).  best(k) is a wave-wide max of the
 //   step before (wf_lanes.h butterfly, DPP and permlane swaps, no LDS).
 //   Bases: per tile of 64 steps a lane takes 32 consecutive columns of its own diagonal, so it
-//   loads one 32-column mismatch word from the bit planes (the chunk's planes of the anchor's
-//   strand, the index's store) and shifts a bit out of it per active step.  The left side
+//   loads one 32-column mismatch word from the bit planes (chunk_mis, wf_mapstore.h: the chunk's
+//   planes of the anchor's strand, the index's store) and shifts a bit out of it per active step.  The left side
 //   reads the words below the anchor, bit-reversed.
 //   Loads: a lane loads a word only when one of its 32 columns lies inside the subject and
 //   inside the contig, so the word starts at most 31 positions before such a column: its first
@@ -30,7 +30,6 @@
 #include "wf_internal.h"
 #include "wf_lanes.h"
 #include "wf_mapstore.h"
-#include "wf_searchstate.h"
 
 namespace wf {
 namespace {
@@ -38,38 +37,14 @@ namespace {
 constexpr int kGapLaunch = 1 << 16;             // anchors per k_search_gapped launch
 constexpr int kGapDead = INT_MIN / 2;
 
-struct GapAnchor { int32_t sm, contig, i0, j0; };   // subject << 1 | minus; i0 on the variant, j0 contig-local
-struct GapSide { int32_t H, p, q, g; };
-struct GapRaw { GapSide left, right; };
-
 struct GapArgs {
   MapIndexView ix;            // the contigs
-  const uint2* vpk[2];        // the chunk: plus store, minus store
-  const uint32_t* vnm[2];
-  const int64_t* off;         // [n_subjects + 1] the subjects' starts in the chunk
-  int64_t total;              // bases of the chunk
+  ChunkView ch;               // the chunk
   int W, X2;                  // band half-width; 2 Xg (half units)
   const GapAnchor* anchor;    // [n]
   int n;
   GapRaw* out;                // [n]
 };
-
-// mismatch bits of the 32 columns whose first lies at position vp of the variant store and gp
-// of the contig store; either may be as low as -32 (the bases before a store are N)
-__device__ __forceinline__ uint32_t gap_mis(const GapArgs& A, int strand, int vp, int gp) {
-  const uint2* pk = A.vpk[strand];
-  const uint32_t* nm = A.vnm[strand];
-  const int Wd = vp >> 5, sh = vp & 31;
-  uint2 a = make_uint2(0u, 0u);
-  uint32_t na = ~0u;
-  if (Wd >= 0) {
-    a = pk[Wd];
-    na = nm[Wd];
-  }
-  const uint2 b = pk[Wd + 1];
-  const uint32_t vlo = window32(a.x, b.x, sh), vhi = window32(a.y, b.y, sh), vn = window32(na, nm[Wd + 1], sh);
-  return map_mis_word<true>(A.ix, &vlo, &vhi, &vn, 0, gp);
-}
 
 __device__ __forceinline__ int wave_max(int x) {
   return wave_butterfly(x, [](int a, int b) { return a > b ? a : b; });
@@ -103,8 +78,8 @@ __device__ __forceinline__ GapSide gap_side(const GapArgs& A, int strand, int vp
       t0 = ((kf - d) >> 1) - 1;
       mis = ~0u;
       if (inband && max(t0, tlo) < min(t0 + 32, thi)) {
-        if (kLeft) mis = __brev(gap_mis(A, strand, vpos - t0 - 31, gpos - d - t0 - 31));
-        else mis = gap_mis(A, strand, vpos + t0, gpos + d + t0);
+        if (kLeft) mis = __brev(chunk_mis(A.ix, A.ch, strand, vpos - t0 - 31, gpos - d - t0 - 31));
+        else mis = chunk_mis(A.ix, A.ch, strand, vpos + t0, gpos + d + t0);
       }
     }
     const bool active = inband && ((k - d) & 1) == 0;
@@ -150,9 +125,8 @@ __global__ __launch_bounds__(256) void k_search_gapped(const GapArgs A) {
   const int lane = threadIdx.x & 63;
   const GapAnchor an = A.anchor[a];
   const int gsub = an.sm >> 1, strand = an.sm & 1;
-  const int64_t o0 = A.off[gsub], o1 = A.off[gsub + 1];
-  const int M = (int)(o1 - o0);
-  const int vbase = (int)(strand ? A.total - o1 : o0);
+  int M, vbase;
+  chunk_place(A.ch, gsub, strand, &M, &vbase);
   const int c0 = A.ix.coff[an.contig], Lc = A.ix.coff[an.contig + 1] - c0;
   // bounds before any load; an anchor outside them (never made by the host) extends nowhere
   const int i0 = min(max(an.i0, 0), M), j0 = min(max(an.j0, 0), Lc);
@@ -161,17 +135,6 @@ __global__ __launch_bounds__(256) void k_search_gapped(const GapArgs A) {
   out.left = gap_side<true>(A, strand, vbase + i0 - 1, c0 + j0 - 1, i0, j0, lane);
   if (lane == 0) A.out[a] = out;
 }
-
-#define GAP_TRY(x)                                                                        \
-  do {                                                                                    \
-    hipError_t e_ = (x);                                                                  \
-    if (e_ != hipSuccess) { *err = std::string(#x) + ": " + hipGetErrorString(e_); return -2; } \
-  } while (0)
-#define GAP_RC(x)                    \
-  do {                               \
-    const int rc_ = (x);             \
-    if (rc_) return rc_;             \
-  } while (0)
 
 struct GapAln {
   int32_t sm, contig, qstart, qspan, sstart, sspan, length, matches, gaps;
@@ -185,29 +148,24 @@ auto aln_key(const GapAln& x) {
 
 int gapped_device(MapState* st, const std::vector<GapAnchor>& anchors, int band, int xdrop_gap, int64_t total,
                   std::vector<GapRaw>* raw, hipStream_t s, std::string* err) {
-  SearchState* ss = st->search;                  // made by search_records: there are anchors
-  GAP_RC(map_ensure(ss->g_anchor, sizeof(GapAnchor) * kGapLaunch, err));
-  GAP_RC(map_ensure(ss->g_out, sizeof(GapRaw) * kGapLaunch, err));
+  SearchState* ss = &st->search;                 // search_records left the chunk in it: there are anchors
+  MAP_RC(ss->g_anchor.ensure(kGapLaunch, err));
+  MAP_RC(ss->g_out.ensure(kGapLaunch, err));
   GapArgs A{};
   A.ix = map_view(st);
-  for (int v = 0; v < 2; ++v) {
-    A.vpk[v] = static_cast<const uint2*>(ss->pk[v].p);
-    A.vnm[v] = static_cast<const uint32_t*>(ss->nm[v].p);
-  }
-  A.off = static_cast<const int64_t*>(ss->off.p);
-  A.total = total;
+  A.ch = chunk_view(*ss, total);
   A.W = band;
   A.X2 = 2 * xdrop_gap;
-  A.anchor = static_cast<const GapAnchor*>(ss->g_anchor.p);
-  A.out = static_cast<GapRaw*>(ss->g_out.p);
+  A.anchor = ss->g_anchor.p;
+  A.out = ss->g_out.p;
   raw->resize(anchors.size());
   for (size_t a0 = 0; a0 < anchors.size(); a0 += kGapLaunch) {
     A.n = (int)std::min<size_t>(kGapLaunch, anchors.size() - a0);
-    GAP_TRY(hipMemcpyAsync(ss->g_anchor.p, anchors.data() + a0, sizeof(GapAnchor) * A.n, hipMemcpyHostToDevice, s));
+    MAP_TRY(hipMemcpyAsync(ss->g_anchor.p, anchors.data() + a0, sizeof(GapAnchor) * A.n, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_search_gapped, dim3((unsigned)((A.n + 3) / 4)), dim3(256), 0, s, A);
-    GAP_TRY(hipGetLastError());
-    GAP_TRY(hipMemcpyAsync(raw->data() + a0, ss->g_out.p, sizeof(GapRaw) * A.n, hipMemcpyDeviceToHost, s));
-    GAP_TRY(hipStreamSynchronize(s));
+    MAP_TRY(hipGetLastError());
+    MAP_TRY(hipMemcpyAsync(raw->data() + a0, ss->g_out.p, sizeof(GapRaw) * A.n, hipMemcpyDeviceToHost, s));
+    MAP_TRY(hipStreamSynchronize(s));
   }
   return 0;
 }
@@ -220,7 +178,7 @@ int search_gapped_run(MapState* st, const char* seq, const int64_t* off, int64_t
   *n = 0;
   *gstats = SearchGapStats{0, 0};
   std::vector<SearchRec> recs;
-  GAP_RC(search_records(st, seq, off, n_subjects, rule, &recs, stats, s, err));
+  MAP_RC(search_records(st, seq, off, n_subjects, rule, &recs, stats, s, err));
   gstats->anchors = (int64_t)recs.size();
   if (recs.empty()) return 0;
   std::vector<GapAnchor> anchors(recs.size());
