@@ -31,7 +31,9 @@ extern "C" {
                                     still 6 (additive): wf_map_index, wf_map_pairs;
                                     still 6 (additive): wf_map_pairs_gapped;
                                     still 6 (additive): wf_search, wf_search_gapped;
-                                    still 6 (additive): wf_search_mask */
+                                    still 6 (additive): wf_search_mask;
+                                    still 6 (additive): wf_search_packed, wf_search_gapped_packed,
+                                                        wf_search_chunk_planes */
 
 enum wf_status {
   WF_OK = 0,
@@ -483,6 +485,40 @@ typedef struct wf_search_gap_result { /* caller-owned host arrays of `capacity` 
    unaffected.  Returns after the work is done. */
 int wf_search_gapped(wf_ctx* ctx, const wf_search_subjects* subjects, const wf_search_params* params,
                      const wf_search_gap_params* gap_params, wf_search_gap_result* out);
+
+/* Subjects as the bit planes of a packed database (python -m waafle_amd.makedb, DESIGN.md
+ * §12.7): the chunk's bases lie bit-contiguously in three planes, starting at bit `bit0` of
+ * their first word, so a slice of a memory-mapped .wfdb file is passed as it is.  A base's code
+ * (A0 C1 G2 T3) is its lo bit + 2 x its hi bit; a set nn bit makes it an N whatever lo and hi
+ * hold there.  The bits before bit0 and from bit0 + off[n_subjects] on belong to the file's
+ * neighbouring subjects and are not searched.  No ASCII is uploaded and nothing is parsed. */
+typedef struct wf_search_packed_subjects { /* host memory; may be a read-only file mapping */
+  int64_t n_subjects;         /* < 2^31 */
+  const int64_t* off;         /* [n_subjects + 1] chunk-relative, off[0] = 0; off[n_subjects] <= 2^30,
+                                 else WF_E_TOOBIG */
+  const uint32_t* lo;         /* base i of the chunk: bit (bit0 + i) & 31 of word (bit0 + i) >> 5 */
+  const uint32_t* hi;
+  const uint32_t* nn;
+  int64_t n_words;            /* (bit0 + off[n_subjects] + 31) / 32; no word outside [0, n_words) is read */
+  int32_t bit0;               /* 0..31 */
+  int32_t _pad;
+} wf_search_packed_subjects;
+
+/* wf_search / wf_search_gapped on such subjects: the same records, counters, statuses and
+   WF_E_NOMEM-and-repeat protocol.  Also WF_E_BADINPUT for bit0 outside 0..31, null planes with
+   off[n_subjects] > 0, or an n_words other than (bit0 + off[n_subjects] + 31) / 32; WF_E_TOOBIG
+   (more than 2^30 bases) is returned before the planes are looked at. */
+int wf_search_packed(wf_ctx* ctx, const wf_search_packed_subjects* subjects, const wf_search_params* params,
+                     wf_search_result* out);
+int wf_search_gapped_packed(wf_ctx* ctx, const wf_search_packed_subjects* subjects, const wf_search_params* params,
+                            const wf_search_gap_params* gap_params, wf_search_gap_result* out);
+
+/* Diagnostic: the device's store of the chunk that the context's last search call (any of the
+   four) left resident, copied out: strand 0 the chunk as given, 1 its reverse complement, each
+   as planes of words = (off[n_subjects] + 31) / 32 + 2 words, the padding N.  A call that found
+   no seed slot (no subject as long as a seed, no index entries) leaves none.  WF_E_STATE when no
+   chunk is resident; WF_E_BADINPUT for another strand, null arrays or another `words`. */
+int wf_search_chunk_planes(wf_ctx* ctx, int strand, uint32_t* lo, uint32_t* hi, uint32_t* nn, int64_t words);
 
 /* Low-complexity masking.  wf_search_mask computes the symmetric-DUST mask
  * (Morgulis et al. 2006, the published definition) of the contigs the context holds and

@@ -4,7 +4,8 @@ one MI355X.
     python scripts/search_bench.py [--contigs 10000 --contig-length 5000 --db-bases 200000000
                                     --subject-length 1000 --homolog-share 0.01 --chunk-bases 67108864
                                     --indel-rate 0.003 --gapped --band 15 --xdrop-gap 30
-                                    --low-complexity 2000 --dust]
+                                    --low-complexity 2000 --dust --packed]
+    python scripts/search_bench.py --files [--tmp-dir DIR]
 
 Not bench.py (the flagship workload); the numbers go to DESIGN.md §12 and profiles/search/.
 The workload is seeded: random contigs, and a database of random subjects of which a share
@@ -26,6 +27,16 @@ min_score 28).  The GPU step runs in a child process under its own time limit
           counts, the share of seed hits skipped by the predecessor shortcut, and the share of
           the planted homologs with at least one record, and with a record that covers at
           least 0.75 of the subject (the scorer's default --min-scov)
+
+  --packed  the same chunks given as the bit planes of a packed database:
+          the subjects are packed once, outside the timing, as `makedb` lays them out, and every
+          chunk is `Searcher.search_packed` (`search_gapped_packed`) on slices of those planes;
+          h2d_bytes_per_chunk is what either form copies to the device for the bases
+  --files   the file leg: the workload written once as FASTA (60-column lines; the contigs too)
+          and once as .wfdb (`makedb`, timed) under a temporary directory, then `search_files`
+          on each, first with the database file's pages evicted (posix_fadvise DONTNEED after
+          fsync: "cold", as far as the file system honours it), then again ("warm"); the two
+          tables must be equal.  Walls include reading the contigs and indexing them.
 
 Prints one JSON line.  For per-kernel times run the step under
 `rocprofv3 --kernel-trace --stats -- python scripts/search_bench.py --step search ...`.
@@ -63,7 +74,10 @@ def parse(argv=None):
     ap.add_argument("--dust", action="store_true", help="wf_search_mask on the contigs before the search")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--gpu", type=int, default=0)
-    ap.add_argument("--step", choices=["search"], help="run the step in this process")
+    ap.add_argument("--packed", action="store_true", help="the subjects as bit planes (wf_search_packed)")
+    ap.add_argument("--files", action="store_true", help="the file leg: search_files on a FASTA and on its .wfdb")
+    ap.add_argument("--tmp-dir", default=None, help="--files: where the temporary directory goes")
+    ap.add_argument("--step", choices=["search", "files"], help="run the step in this process")
     ap.add_argument("--step-timeout", type=int, default=600, help="seconds for the GPU step")
     return ap.parse_args(argv)
 
@@ -116,11 +130,27 @@ def make_workload(a):
     return codes, off, subj, hom
 
 
+def pack_subjects(subj):
+    """[n, L] codes as a makedb would lay them out: (off, lo, hi, nn), a database in memory"""
+    import types
+    from waafle_amd import makedb
+    n, L = subj.shape
+    rows = max((1 << 25) // L // 32 * 32, 32)                 # whole words per piece
+    parts = []
+    for lo in range(0, n, rows):
+        bases = ASCII[subj[lo:lo + rows]].reshape(-1)
+        parts.append(makedb.pack_words(np.concatenate([bases, np.zeros(-len(bases) % 32, np.uint8)])))
+    parts.append(makedb.pack_words(np.zeros(64, np.uint8)))  # the two padding words
+    lo, hi, nn = (np.concatenate([p[k] for p in parts]) for k in range(3))
+    return types.SimpleNamespace(off=np.arange(n + 1, dtype=np.int64) * L, lo=lo, hi=hi, nn=nn)
+
+
 def step_search(a):
     from waafle_amd import search
     codes, off, subj, hom = make_workload(a)
     n, L = subj.shape
     per = max(a.chunk_bases // L, 1)
+    db = pack_subjects(subj) if a.packed else None
     walls, records, found, span = [], 0, np.zeros(n, bool), np.zeros(n, np.int64)
     gap = dict(band=a.band, xdrop_gap=a.xdrop_gap) if a.gapped else {}
     dust = {}
@@ -134,15 +164,27 @@ def step_search(a):
             s.apply_mask(len(codes))                          # again, with everything allocated
             dust["mask_call_again_s"] = time.perf_counter() - t0
         run = s.search_gapped if a.gapped else s.search
+        run_packed = s.search_gapped_packed if a.gapped else s.search_packed
         w = min(n, max((1 << 20) // L, 1))
-        run(ASCII[subj[:w]].reshape(-1), np.arange(w + 1, dtype=np.int64) * L)          # warm-up chunk
+        if a.packed:                                          # warm-up chunk
+            run_packed(search.PackedChunk(db, 0, w))
+        else:
+            run(ASCII[subj[:w]].reshape(-1), np.arange(w + 1, dtype=np.int64) * L)
         s.stats = dict.fromkeys(s.stats, 0)
+        copied = []
         for lo in range(0, n, per):
             hi = min(lo + per, n)
-            seq = ASCII[subj[lo:hi]].reshape(-1)
-            soff = np.arange(hi - lo + 1, dtype=np.int64) * L
-            t0 = time.perf_counter()
-            rec = run(seq, soff)
+            if a.packed:
+                chunk = search.PackedChunk(db, lo, hi)
+                copied.append(12 * len(chunk.lo))
+                t0 = time.perf_counter()
+                rec = run_packed(chunk)
+            else:
+                seq = ASCII[subj[lo:hi]].reshape(-1)
+                soff = np.arange(hi - lo + 1, dtype=np.int64) * L
+                copied.append(len(seq))
+                t0 = time.perf_counter()
+                rec = run(seq, soff)
             walls.append(time.perf_counter() - t0)
             records += len(rec["contig"])
             found[rec["subject"].astype(np.int64) + lo] = True
@@ -152,6 +194,7 @@ def step_search(a):
     return dict(search_s=total, chunk_s=walls, chunk_bases=per * L, subject_bases_per_s=n * L / total,
                 subjects=n, homologs=int(len(hom)), homologs_found_fraction=float(found[hom].mean()) if len(hom) else 0.0,
                 homologs_scov_075=int((span[hom] >= 0.75 * L).sum()), gapped=bool(a.gapped),
+                packed=bool(a.packed), h2d_bytes_per_chunk=copied,
                 anchors=stats.get("anchors", 0), raw_alignments=stats.get("raw_alignments", 0),
                 other_subjects_with_records=int(found.sum() - found[hom].sum()), records=records,
                 seed_hits=stats["seed_hits"], seeds_skipped=stats["seeds_skipped"], raw_hsps=stats["raw_hsps"],
@@ -160,18 +203,77 @@ def step_search(a):
                        "one warm-up chunk")
 
 
+def evict(path):
+    """Ask the kernel to drop the file's cached pages (they are clean after the fsync)."""
+    fd = os.open(path, os.O_RDONLY)
+    try:
+        os.fsync(fd)
+        os.posix_fadvise(fd, 0, 0, os.POSIX_FADV_DONTNEED)
+    finally:
+        os.close(fd)
+
+
+def step_files(a):
+    import shutil
+    import tempfile
+    from waafle_amd import makedb, search
+    codes, off, subj, hom = make_workload(a)
+    n, L = subj.shape
+    d = tempfile.mkdtemp(prefix="search_bench_", dir=a.tmp_dir)
+    out = dict(tmp_dir=d, subjects=n, db_bases=n * L)
+    try:
+        query, fasta, wfdb = (os.path.join(d, f) for f in ("contigs.fna", "genes.fna", "genes.wfdb"))
+
+        def write_fasta(path, rows, name):
+            with open(path, "wb") as fh:
+                for i, row in enumerate(rows):
+                    text = ASCII[row].tobytes()
+                    fh.write(name(i) + b"\n".join(text[k:k + 60] for k in range(0, len(text), 60)) + b"\n")
+
+        write_fasta(query, (codes[off[c]:off[c + 1]] for c in range(a.contigs)), lambda i: b">ctg%d\n" % i)
+        t0 = time.perf_counter()
+        write_fasta(fasta, subj, lambda i: b">g%d|s__S%d|UniProt=U%d\n" % (i, i % 97, i))
+        out["write_fasta_s"] = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        makedb.make_db(fasta, wfdb)
+        out["makedb_s"] = time.perf_counter() - t0
+        out["fasta_bytes"], out["wfdb_bytes"] = os.path.getsize(fasta), os.path.getsize(wfdb)
+        gap = dict(gapped=True, band=a.band, xdrop_gap=a.xdrop_gap) if a.gapped else {}
+        t0 = time.perf_counter()
+        search.mapper.read_fasta(query)
+        out["read_contigs_s"] = time.perf_counter() - t0      # part of every wall below
+        tables = {}
+        for cache in ("cold", "warm"):
+            for form, db in (("fasta", fasta), ("wfdb", wfdb)):
+                if cache == "cold":
+                    evict(db)
+                table = os.path.join(d, form + ".blastout")
+                t0 = time.perf_counter()
+                st = search.search_files(query, db, table, device=a.gpu, chunk_bases=a.chunk_bases, dust=a.dust, **gap)
+                out["search_files_{}_{}_s".format(form, cache)] = time.perf_counter() - t0
+                out["rows"] = st["rows"]
+                tables[form] = open(table, "rb").read()
+            out["tables_equal_" + cache] = tables["fasta"] == tables["wfdb"]
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+    out["cache"] = "cold: the database file's pages evicted by posix_fadvise(DONTNEED) after fsync, the contigs' " \
+                   "file left cached; warm: the same call again"
+    return out
+
+
 def main(argv=None):
     a = parse(argv)
     if a.step:
-        print("SEARCH_BENCH_STEP " + json.dumps(step_search(a)))
+        print("SEARCH_BENCH_STEP " + json.dumps(step_files(a) if a.step == "files" else step_search(a)))
         return 0
     out = dict(workload=dict(contigs=a.contigs, contig_length=a.contig_length, db_bases=a.db_bases,
                              subject_length=a.subject_length, homolog_share=a.homolog_share,
                              identity="90..100 %", indel_rate=a.indel_rate, seed=a.seed, gapped=a.gapped,
                              band=a.band, xdrop_gap=a.xdrop_gap, low_complexity=a.low_complexity, dust=a.dust,
+                             packed=a.packed, files=a.files,
                              params=dict(seed_length=21, seed_stride=8, max_seed_hits=64, xdrop=20, min_score=28)))
     passed = [x for x in (argv if argv is not None else sys.argv[1:])]
-    cmd = [sys.executable, os.path.abspath(__file__), "--step", "search"] + passed
+    cmd = [sys.executable, os.path.abspath(__file__), "--step", "files" if a.files else "search"] + passed
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=a.step_timeout, cwd=REPO)
     except subprocess.TimeoutExpired:

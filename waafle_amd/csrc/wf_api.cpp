@@ -766,41 +766,67 @@ int wf_map_pairs_gapped(wf_ctx* ctx, const wf_map_reads* rd, const wf_map_params
   return rc ? fail(ctx, rc, "%s", err.c_str()) : WF_OK;
 }
 
-// the checks wf_search and wf_search_gapped share; *run: there is work to do
-static int check_search_call(wf_ctx* ctx, const wf_search_subjects* sb, const wf_search_params* p, int64_t capacity,
-                             const char* name, bool* run) {
+// the checks the search calls share, whichever form the bases come in; *run: there is work
+// to do, and then *total = off[n_subjects].  The caller checks its bases after it.
+static int check_search_call(wf_ctx* ctx, int64_t n_subjects, const int64_t* off, const wf_search_params* p,
+                             int64_t capacity, const char* name, bool* run, int64_t* total_out) {
   *run = false;
+  *total_out = 0;
   if (p->seed_len < 12 || p->seed_len > 32) return fail(ctx, WF_E_BADINPUT, "seed_len %d outside 12..32", p->seed_len);
   if (p->stride < 1 || p->stride > 32) return fail(ctx, WF_E_BADINPUT, "stride %d outside 1..32", p->stride);
   if (p->max_occ < 1 || p->max_occ > 1024) return fail(ctx, WF_E_BADINPUT, "max_occ %d outside 1..1024", p->max_occ);
   if (p->xdrop < 1 || p->xdrop > 1000) return fail(ctx, WF_E_BADINPUT, "xdrop %d outside 1..1000", p->xdrop);
   if (p->min_score < 1) return fail(ctx, WF_E_BADINPUT, "min_score %d below 1", p->min_score);
-  if (sb->n_subjects < 0 || sb->n_subjects >= ((int64_t)1 << 31))
+  if (n_subjects < 0 || n_subjects >= ((int64_t)1 << 31))
     return fail(ctx, WF_E_BADINPUT, "n_subjects outside [0, 2^31)");
   if (capacity < 0) return fail(ctx, WF_E_BADINPUT, "negative capacity");
   int S = 0, occ = 0;
   if (!wf::map_index_params(ctx->map, &S, &occ)) return fail(ctx, WF_E_STATE, "%s before wf_map_index", name);
   if (S != p->seed_len) return fail(ctx, WF_E_BADINPUT, "seed_len %d differs from the index's %d", p->seed_len, S);
-  if (sb->n_subjects == 0) return WF_OK;
-  if (!sb->off) return fail(ctx, WF_E_BADINPUT, "null subject offsets");
-  if (sb->off[0] != 0) return fail(ctx, WF_E_BADINPUT, "subject offsets must start at 0");
-  for (int64_t i = 0; i < sb->n_subjects; ++i)
-    if (sb->off[i + 1] < sb->off[i]) return fail(ctx, WF_E_BADINPUT, "subject offsets decrease at subject %lld", (long long)i);
-  const int64_t total = sb->off[sb->n_subjects];
+  if (n_subjects == 0) return WF_OK;
+  if (!off) return fail(ctx, WF_E_BADINPUT, "null subject offsets");
+  if (off[0] != 0) return fail(ctx, WF_E_BADINPUT, "subject offsets must start at 0");
+  for (int64_t i = 0; i < n_subjects; ++i)
+    if (off[i + 1] < off[i]) return fail(ctx, WF_E_BADINPUT, "subject offsets decrease at subject %lld", (long long)i);
+  const int64_t total = off[n_subjects];
   if (total > ((int64_t)1 << 30)) return fail(ctx, WF_E_TOOBIG, "a chunk of %lld bases (at most 2^30)", (long long)total);
+  *total_out = total;
+  *run = true;
+  return WF_OK;
+}
+
+static int check_search_ascii(wf_ctx* ctx, const wf_search_subjects* sb, const wf_search_params* p, int64_t capacity,
+                              const char* name, bool* run) {
+  int64_t total = 0;
+  const int rc = check_search_call(ctx, sb->n_subjects, sb->off, p, capacity, name, run, &total);
+  if (rc || !*run) return rc;
+  *run = false;
   if (total > 0 && !sb->seq) return fail(ctx, WF_E_BADINPUT, "null subject bases");
   *run = true;
   return WF_OK;
 }
 
-int wf_search(wf_ctx* ctx, const wf_search_subjects* sb, const wf_search_params* p, wf_search_result* r) {
-  if (!ctx) return WF_E_BADINPUT;
-  if (!sb || !p || !r) return fail(ctx, WF_E_BADINPUT, "null subjects/params/result");
-  r->n = 0;
-  r->seed_hits = r->seeds_skipped = r->raw_hsps = 0;
-  bool run = false;
-  int rc = check_search_call(ctx, sb, p, r->capacity, "wf_search", &run);
-  if (rc || !run) return rc;
+// bit0 is checked first: it needs no index and no offsets.  Nothing of the planes is read here.
+static int check_search_packed(wf_ctx* ctx, const wf_search_packed_subjects* sb, const wf_search_params* p,
+                               int64_t capacity, const char* name, bool* run) {
+  *run = false;
+  if (sb->bit0 < 0 || sb->bit0 > 31) return fail(ctx, WF_E_BADINPUT, "bit0 %d outside 0..31", sb->bit0);
+  int64_t total = 0;
+  const int rc = check_search_call(ctx, sb->n_subjects, sb->off, p, capacity, name, run, &total);
+  if (rc || !*run) return rc;
+  *run = false;
+  if (total > 0 && (!sb->lo || !sb->hi || !sb->nn)) return fail(ctx, WF_E_BADINPUT, "null subject planes");
+  const int64_t want = (sb->bit0 + total + 31) / 32;
+  if (sb->n_words != want)
+    return fail(ctx, WF_E_BADINPUT, "n_words %lld, but bit0 %d and %lld bases make %lld", (long long)sb->n_words,
+                sb->bit0, (long long)total, (long long)want);
+  *run = true;
+  return WF_OK;
+}
+
+// the two search calls proper, after their checks
+static int run_search(wf_ctx* ctx, const wf::ChunkSource& src, const int64_t* off, int64_t n_subjects,
+                      const wf_search_params* p, wf_search_result* r) {
   if (r->capacity > 0 && (!r->contig || !r->subject || !r->minus || !r->qstart || !r->sstart || !r->length ||
                           !r->matches))
     return fail(ctx, WF_E_BADINPUT, "null result arrays");
@@ -809,7 +835,7 @@ int wf_search(wf_ctx* ctx, const wf_search_subjects* sb, const wf_search_params*
   const wf::SearchOut out{r->capacity, r->contig, r->subject, r->minus, r->qstart, r->sstart, r->length, r->matches};
   wf::SearchStats stats{0, 0, 0};
   std::string err;
-  rc = wf::search_run(ctx->map, sb->seq, sb->off, sb->n_subjects, rule, out, &r->n, &stats, ctx->stream, &err);
+  const int rc = wf::search_run(ctx->map, src, off, n_subjects, rule, out, &r->n, &stats, ctx->stream, &err);
   if (rc) return fail(ctx, rc, "%s", err.c_str());
   r->seed_hits = stats.seed_hits;
   r->seeds_skipped = stats.skipped;
@@ -819,18 +845,8 @@ int wf_search(wf_ctx* ctx, const wf_search_subjects* sb, const wf_search_params*
   return WF_OK;
 }
 
-int wf_search_gapped(wf_ctx* ctx, const wf_search_subjects* sb, const wf_search_params* p,
-                     const wf_search_gap_params* gp, wf_search_gap_result* r) {
-  if (!ctx) return WF_E_BADINPUT;
-  if (!sb || !p || !gp || !r) return fail(ctx, WF_E_BADINPUT, "null subjects/params/gap params/result");
-  r->n = 0;
-  r->seed_hits = r->seeds_skipped = r->raw_hsps = r->anchors = r->raw_alignments = 0;
-  if (gp->band < 1 || gp->band > 31) return fail(ctx, WF_E_BADINPUT, "band %d outside 1..31", gp->band);
-  if (gp->xdrop_gap < 1 || gp->xdrop_gap > 1000)
-    return fail(ctx, WF_E_BADINPUT, "xdrop_gap %d outside 1..1000", gp->xdrop_gap);
-  bool run = false;
-  int rc = check_search_call(ctx, sb, p, r->capacity, "wf_search_gapped", &run);
-  if (rc || !run) return rc;
+static int run_search_gapped(wf_ctx* ctx, const wf::ChunkSource& src, const int64_t* off, int64_t n_subjects,
+                             const wf_search_params* p, const wf_search_gap_params* gp, wf_search_gap_result* r) {
   if (r->capacity > 0 && (!r->contig || !r->subject || !r->minus || !r->qstart || !r->qspan || !r->sstart ||
                           !r->sspan || !r->length || !r->matches || !r->gaps))
     return fail(ctx, WF_E_BADINPUT, "null result arrays");
@@ -841,8 +857,8 @@ int wf_search_gapped(wf_ctx* ctx, const wf_search_subjects* sb, const wf_search_
   wf::SearchStats stats{0, 0, 0};
   wf::SearchGapStats gstats{0, 0};
   std::string err;
-  rc = wf::search_gapped_run(ctx->map, sb->seq, sb->off, sb->n_subjects, rule, gp->band, gp->xdrop_gap, out, &r->n,
-                             &stats, &gstats, ctx->stream, &err);
+  const int rc = wf::search_gapped_run(ctx->map, src, off, n_subjects, rule, gp->band, gp->xdrop_gap, out, &r->n,
+                                       &stats, &gstats, ctx->stream, &err);
   if (rc) return fail(ctx, rc, "%s", err.c_str());
   r->seed_hits = stats.seed_hits;
   r->seeds_skipped = stats.skipped;
@@ -852,6 +868,82 @@ int wf_search_gapped(wf_ctx* ctx, const wf_search_subjects* sb, const wf_search_
   if (r->n > r->capacity)
     return fail(ctx, WF_E_NOMEM, "%lld records, room for %lld", (long long)r->n, (long long)r->capacity);
   return WF_OK;
+}
+
+// the part of wf_search_gapped's checks that comes before the shared ones
+static int check_gap_params(wf_ctx* ctx, const wf_search_gap_params* gp) {
+  if (gp->band < 1 || gp->band > 31) return fail(ctx, WF_E_BADINPUT, "band %d outside 1..31", gp->band);
+  if (gp->xdrop_gap < 1 || gp->xdrop_gap > 1000)
+    return fail(ctx, WF_E_BADINPUT, "xdrop_gap %d outside 1..1000", gp->xdrop_gap);
+  return WF_OK;
+}
+
+int wf_search(wf_ctx* ctx, const wf_search_subjects* sb, const wf_search_params* p, wf_search_result* r) {
+  if (!ctx) return WF_E_BADINPUT;
+  if (!sb || !p || !r) return fail(ctx, WF_E_BADINPUT, "null subjects/params/result");
+  r->n = 0;
+  r->seed_hits = r->seeds_skipped = r->raw_hsps = 0;
+  bool run = false;
+  const int rc = check_search_ascii(ctx, sb, p, r->capacity, "wf_search", &run);
+  if (rc || !run) return rc;
+  return run_search(ctx, wf::ChunkSource{sb->seq, nullptr, nullptr, nullptr, 0, 0}, sb->off, sb->n_subjects, p, r);
+}
+
+int wf_search_packed(wf_ctx* ctx, const wf_search_packed_subjects* sb, const wf_search_params* p,
+                     wf_search_result* r) {
+  if (!ctx) return WF_E_BADINPUT;
+  if (!sb || !p || !r) return fail(ctx, WF_E_BADINPUT, "null subjects/params/result");
+  r->n = 0;
+  r->seed_hits = r->seeds_skipped = r->raw_hsps = 0;
+  bool run = false;
+  const int rc = check_search_packed(ctx, sb, p, r->capacity, "wf_search_packed", &run);
+  if (rc || !run) return rc;
+  return run_search(ctx, wf::ChunkSource{nullptr, sb->lo, sb->hi, sb->nn, sb->n_words, sb->bit0}, sb->off,
+                    sb->n_subjects, p, r);
+}
+
+int wf_search_gapped(wf_ctx* ctx, const wf_search_subjects* sb, const wf_search_params* p,
+                     const wf_search_gap_params* gp, wf_search_gap_result* r) {
+  if (!ctx) return WF_E_BADINPUT;
+  if (!sb || !p || !gp || !r) return fail(ctx, WF_E_BADINPUT, "null subjects/params/gap params/result");
+  r->n = 0;
+  r->seed_hits = r->seeds_skipped = r->raw_hsps = r->anchors = r->raw_alignments = 0;
+  int rc = check_gap_params(ctx, gp);
+  if (rc) return rc;
+  bool run = false;
+  rc = check_search_ascii(ctx, sb, p, r->capacity, "wf_search_gapped", &run);
+  if (rc || !run) return rc;
+  return run_search_gapped(ctx, wf::ChunkSource{sb->seq, nullptr, nullptr, nullptr, 0, 0}, sb->off, sb->n_subjects, p,
+                           gp, r);
+}
+
+int wf_search_gapped_packed(wf_ctx* ctx, const wf_search_packed_subjects* sb, const wf_search_params* p,
+                            const wf_search_gap_params* gp, wf_search_gap_result* r) {
+  if (!ctx) return WF_E_BADINPUT;
+  if (!sb || !p || !gp || !r) return fail(ctx, WF_E_BADINPUT, "null subjects/params/gap params/result");
+  r->n = 0;
+  r->seed_hits = r->seeds_skipped = r->raw_hsps = r->anchors = r->raw_alignments = 0;
+  int rc = check_gap_params(ctx, gp);
+  if (rc) return rc;
+  bool run = false;
+  rc = check_search_packed(ctx, sb, p, r->capacity, "wf_search_gapped_packed", &run);
+  if (rc || !run) return rc;
+  return run_search_gapped(ctx, wf::ChunkSource{nullptr, sb->lo, sb->hi, sb->nn, sb->n_words, sb->bit0}, sb->off,
+                           sb->n_subjects, p, gp, r);
+}
+
+int wf_search_chunk_planes(wf_ctx* ctx, int strand, uint32_t* lo, uint32_t* hi, uint32_t* nn, int64_t words) {
+  if (!ctx) return WF_E_BADINPUT;
+  if (strand != 0 && strand != 1) return fail(ctx, WF_E_BADINPUT, "strand %d is neither 0 nor 1", strand);
+  if (!lo || !hi || !nn) return fail(ctx, WF_E_BADINPUT, "null plane arrays");
+  const int64_t have = wf::search_chunk_words(ctx->map);
+  if (have == 0) return fail(ctx, WF_E_STATE, "wf_search_chunk_planes: no chunk is resident");
+  if (words != have)
+    return fail(ctx, WF_E_BADINPUT, "%lld words, but the resident chunk has %lld", (long long)words, (long long)have);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  std::string err;
+  const int rc = wf::search_chunk_planes(ctx->map, strand, lo, hi, nn, ctx->stream, &err);
+  return rc ? fail(ctx, rc, "%s", err.c_str()) : WF_OK;
 }
 
 int wf_search_mask(wf_ctx* ctx, const wf_dust_params* p, wf_dust_result* r) {

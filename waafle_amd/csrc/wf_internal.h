@@ -203,7 +203,17 @@ struct SearchOut {
   int32_t* matches;
 };
 struct SearchStats { int64_t seed_hits, skipped, raw_hsps; };
-int search_run(MapState* st, const char* seq, const int64_t* off, int64_t n_subjects, const SearchRule& rule,
+// The bases of a chunk, in host memory: seq, total ASCII bytes; or, with seq null, the three
+// bit planes of a packed database: base i of the chunk is bit (bit0 + i) & 31
+// of word (bit0 + i) >> 5, no word outside [0, n_words) is read, and the bits around the chunk
+// (its neighbours in the file) do not reach the store.
+struct ChunkSource {
+  const char* seq;
+  const uint32_t* lo; const uint32_t* hi; const uint32_t* nn;
+  int64_t n_words;
+  int bit0;
+};
+int search_run(MapState* st, const ChunkSource& src, const int64_t* off, int64_t n_subjects, const SearchRule& rule,
                const SearchOut& out, int64_t* n, SearchStats* stats, hipStream_t s, std::string* err);
 // ... with every record extended as an anchor by the banded gapped rule of DESIGN.md §12.5
 // (wf_search_gap.hip).  The records come back sorted by (contig, subject, minus, qstart,
@@ -214,9 +224,15 @@ struct SearchGapOut {
   int32_t* sspan; int32_t* length; int32_t* matches; int32_t* gaps;
 };
 struct SearchGapStats { int64_t anchors, raw_alignments; };
-int search_gapped_run(MapState* st, const char* seq, const int64_t* off, int64_t n_subjects, const SearchRule& rule,
+int search_gapped_run(MapState* st, const ChunkSource& src, const int64_t* off, int64_t n_subjects, const SearchRule& rule,
                       int band, int xdrop_gap, const SearchGapOut& out, int64_t* n, SearchStats* stats,
                       SearchGapStats* gstats, hipStream_t s, std::string* err);
+// The chunk the last search call left resident: its store words per plane, (total + 31) / 32 +
+// 2, or 0 when none is; and its planes of `strand` copied to the host (lo, hi, nn: that many
+// words each).
+int64_t search_chunk_words(const MapState* st);
+int search_chunk_planes(MapState* st, int strand, uint32_t* lo, uint32_t* hi, uint32_t* nn, hipStream_t s,
+                        std::string* err);
 
 // low-complexity mask (wf_dust.hip): the symmetric-DUST mask of the contigs
 // the state holds, kept in the state, and the index rebuilt without the S-mers that hold a

@@ -88,6 +88,8 @@ struct SearchState {
   DevArr<unsigned long long> ctr;
   DevArr<GapAnchor> g_anchor;  // the gapped extension's anchors and results of one launch
   DevArr<GapRaw> g_out;
+  DevArr<uint32_t> planes;     // a packed chunk as uploaded: lo, hi, nn, n_words each (k_search_unpack reads it)
+  int64_t resident = -1;       // bases of the chunk whose planes pk, nm hold; -1: none
 };
 
 struct MapState {
@@ -162,8 +164,9 @@ int map_build_index(MapState* st, const uint32_t* dm, hipStream_t s, std::string
 ChunkView chunk_view(const SearchState& ss, int64_t total);
 // The ungapped records of the chunk, sorted by (contig, subject, minus,
 // qstart, sstart, length).  When any seed slot exists, the chunk's bit planes (pk, nm of both
-// strands) and `off` stay resident in st->search afterwards.
-int search_records(MapState* st, const char* seq, const int64_t* off, int64_t n_subjects, const SearchRule& rule,
+// strands) and `off` stay resident in st->search afterwards (SearchState::resident), whichever
+// form src gave the bases in.
+int search_records(MapState* st, const ChunkSource& src, const int64_t* off, int64_t n_subjects, const SearchRule& rule,
                    std::vector<SearchRec>* recs, SearchStats* stats, hipStream_t s, std::string* err);
 
 // ---- device helpers -----------------------------------------------------------------------

@@ -8,6 +8,9 @@
 //   map_pack twice   (k_map_pack, wf_map.hip) the chunk as bit planes in both orientations:
 //                    the minus store is the reverse complement of the whole chunk, so subject
 //                    [o, o') lies at [total - o', total - o) in it, reverse-complemented
+//   or, for a chunk given as the bit planes of a packed database (ChunkSource):
+//   k_search_unpack  thread per store word: the same two stores from the three planes as they
+//                    lie in the file, at any bit offset; no ASCII on the device
 //   then, per tile of at most kSearchTile seed slots (slot = strand, subject, offset a = kT):
 //   k_search_count   thread per slot: the S-mer of the variant, its bucket, the first of its
 //                    occurrences in the sorted index and their number (0 when the seed holds
@@ -178,8 +181,83 @@ __global__ __launch_bounds__(256) void k_search_extend(const SearchArgs A) {
   A.raw[atomicAdd(&A.ctr[0], 1ull)] = out;       // at most nh <= kSearchLaunch per launch
 }
 
+struct UnpackArgs {
+  const uint32_t* in[3];      // lo, hi, nn as uploaded: [n_words] each
+  int64_t n_words;
+  int64_t total;              // bases of the chunk; base i is bit bit0 + i of the planes
+  int64_t words;              // (total + 31) / 32 + 2 store words per strand
+  int bit0;
+  uint2* pk[2];
+  uint32_t* nm[2];
+};
+
+// bits [b, b + 32) of plane p, b >= -31; the words outside [0, n_words) are not loaded and
+// read as 0 (the caller makes those positions N)
+__device__ __forceinline__ uint32_t unpack_window(const uint32_t* p, int64_t n_words, int64_t b) {
+  const int64_t W = b >> 5;                      // floor: -1 for a negative b
+  const int sh = (int)(b & 31);
+  const uint32_t x = W >= 0 && W < n_words ? p[W] : 0u;
+  const uint32_t y = sh && W + 1 < n_words ? p[W + 1] : 0u;
+  return window32(x, y, sh);
+}
+
+// Store word w of both strands from the file's planes.  Plus: chunk positions [32 w, 32 w + 32),
+// the window at bit bit0 + 32 w.  Minus: positions total - 1 - 32 w downwards, complemented: the
+// window at bit0 + total - 32 (w + 1) (negative by up to 31 bits in the last word with bases),
+// bit-reversed, both base planes flipped.  Either way bit k is a base of the chunk exactly when
+// k < total - 32 w, so one mask serves both; every other bit is N, and lo, hi are cleared under
+// N here, whatever the file holds.  A word without bases loads nothing.
+__global__ __launch_bounds__(256) void k_search_unpack(const UnpackArgs A) {
+  const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= A.words) return;
+  const int64_t left = A.total - 32 * w;
+  uint32_t plo = 0, phi = 0, pn = ~0u, mlo = 0, mhi = 0, mn = ~0u;
+  if (left > 0) {
+    const uint32_t pad = left < 32 ? ~0u << (int)left : 0u;
+    const int64_t bp = A.bit0 + 32 * w, bm = A.bit0 + left - 32;
+    pn = unpack_window(A.in[2], A.n_words, bp) | pad;
+    plo = unpack_window(A.in[0], A.n_words, bp) & ~pn;
+    phi = unpack_window(A.in[1], A.n_words, bp) & ~pn;
+    mn = __brev(unpack_window(A.in[2], A.n_words, bm)) | pad;
+    mlo = ~__brev(unpack_window(A.in[0], A.n_words, bm)) & ~mn;
+    mhi = ~__brev(unpack_window(A.in[1], A.n_words, bm)) & ~mn;
+  }
+  A.pk[0][w] = make_uint2(plo, phi);
+  A.nm[0][w] = pn;
+  A.pk[1][w] = make_uint2(mlo, mhi);
+  A.nm[1][w] = mn;
+}
+
+// the chunk's stores pk, nm of both strands from src, enqueued on s; search_device has made
+// room in ss->seq or ss->planes
+int search_store(SearchState* ss, const ChunkSource& src, int64_t total, hipStream_t s, std::string* err) {
+  if (src.seq) {
+    MAP_TRY(hipMemcpyAsync(ss->seq.p, src.seq, (size_t)total, hipMemcpyHostToDevice, s));
+    for (int v = 0; v < 2; ++v) MAP_RC(map_pack(ss->seq.p, total, v == 1, ss->pk[v].p, ss->nm[v].p, s, err));
+    return 0;
+  }
+  UnpackArgs U{};
+  U.n_words = src.n_words;
+  U.total = total;
+  U.words = (total + 31) / 32 + 2;
+  U.bit0 = src.bit0;
+  const uint32_t* from[3] = {src.lo, src.hi, src.nn};
+  for (int k = 0; k < 3; ++k) {
+    uint32_t* to = ss->planes.p + (size_t)k * src.n_words;
+    MAP_TRY(hipMemcpyAsync(to, from[k], sizeof(uint32_t) * (size_t)src.n_words, hipMemcpyHostToDevice, s));
+    U.in[k] = to;
+  }
+  for (int v = 0; v < 2; ++v) {
+    U.pk[v] = ss->pk[v].p;
+    U.nm[v] = ss->nm[v].p;
+  }
+  hipLaunchKernelGGL(k_search_unpack, dim3((unsigned)((U.words + 255) / 256)), dim3(256), 0, s, U);
+  MAP_TRY(hipGetLastError());
+  return 0;
+}
+
 // the seed hits of the chunk, extended: appended to *raw
-int search_device(MapState* st, const char* seq, const int64_t* off, int64_t n, const SearchRule& rule,
+int search_device(MapState* st, const ChunkSource& src, const int64_t* off, int64_t n, const SearchRule& rule,
                   std::vector<SearchRaw>* raw, SearchStats* stats, hipStream_t s, std::string* err) {
   SearchState* ss = &st->search;
   const int64_t total = off[n];
@@ -194,7 +272,8 @@ int search_device(MapState* st, const char* seq, const int64_t* off, int64_t n, 
   const int64_t words = (total + 31) / 32 + 2;
   const int tile = (int)std::min<int64_t>(kSearchTile, kSearchTileHits / rule.max_occ);
   const int64_t tile_cap = std::min<int64_t>(tile, 2 * NS);
-  MAP_RC(ss->seq.ensure(total, err));
+  if (src.seq) MAP_RC(ss->seq.ensure(total, err));           // ss->seq is not touched by a packed chunk
+  else MAP_RC(ss->planes.ensure(3 * (size_t)src.n_words, err));
   MAP_RC(ss->off.ensure(n + 1, err));
   MAP_RC(ss->soff.ensure(n + 1, err));
   for (int v = 0; v < 2; ++v) {
@@ -207,10 +286,10 @@ int search_device(MapState* st, const char* seq, const int64_t* off, int64_t n, 
   MAP_RC(ss->raw.ensure(kSearchLaunch, err));
   MAP_RC(ss->ctr.ensure(2, err));
   MAP_RC(scan_reserve(ss->tmp, (int)tile_cap, s, err));      // the largest tile: the loop allocates nothing
-  MAP_TRY(hipMemcpyAsync(ss->seq.p, seq, (size_t)total, hipMemcpyHostToDevice, s));
   MAP_TRY(hipMemcpyAsync(ss->off.p, off, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, s));
   MAP_TRY(hipMemcpyAsync(ss->soff.p, soff.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, s));
-  for (int v = 0; v < 2; ++v) MAP_RC(map_pack(ss->seq.p, total, v == 1, ss->pk[v].p, ss->nm[v].p, s, err));
+  MAP_RC(search_store(ss, src, total, s, err));
+  ss->resident = total;
 
   SearchArgs A{};
   A.ix = map_view(st);
@@ -262,14 +341,15 @@ ChunkView chunk_view(const SearchState& ss, int64_t total) {
   return ChunkView{{ss.pk[0].p, ss.pk[1].p}, {ss.nm[0].p, ss.nm[1].p}, ss.off.p, total};
 }
 
-int search_records(MapState* st, const char* seq, const int64_t* off, int64_t n_subjects, const SearchRule& rule,
+int search_records(MapState* st, const ChunkSource& src, const int64_t* off, int64_t n_subjects, const SearchRule& rule,
                    std::vector<SearchRec>* recs_out, SearchStats* stats, hipStream_t s, std::string* err) {
   std::vector<SearchRec>& recs = *recs_out;
   recs.clear();
   *stats = SearchStats{0, 0, 0};
+  st->search.resident = -1;
   if (n_subjects == 0 || st->n_kmers == 0) return 0;
   std::vector<SearchRaw> raw;
-  const int rc = search_device(st, seq, off, n_subjects, rule, &raw, stats, s, err);
+  const int rc = search_device(st, src, off, n_subjects, rule, &raw, stats, s, err);
   if (rc) {
     (void)hipStreamSynchronize(s);
     return rc;
@@ -301,11 +381,11 @@ int search_records(MapState* st, const char* seq, const int64_t* off, int64_t n_
   return 0;
 }
 
-int search_run(MapState* st, const char* seq, const int64_t* off, int64_t n_subjects, const SearchRule& rule,
+int search_run(MapState* st, const ChunkSource& src, const int64_t* off, int64_t n_subjects, const SearchRule& rule,
                const SearchOut& out, int64_t* n, SearchStats* stats, hipStream_t s, std::string* err) {
   *n = 0;
   std::vector<SearchRec> recs;
-  const int rc = search_records(st, seq, off, n_subjects, rule, &recs, stats, s, err);
+  const int rc = search_records(st, src, off, n_subjects, rule, &recs, stats, s, err);
   if (rc) return rc;
   *n = (int64_t)recs.size();
   const int64_t w = std::min<int64_t>(*n, out.capacity);
@@ -318,6 +398,24 @@ int search_run(MapState* st, const char* seq, const int64_t* off, int64_t n_subj
     out.sstart[i] = r.sstart;
     out.length[i] = r.length;
     out.matches[i] = r.matches;
+  }
+  return 0;
+}
+
+int64_t search_chunk_words(const MapState* st) {
+  return !st || st->search.resident < 0 ? 0 : (st->search.resident + 31) / 32 + 2;
+}
+
+int search_chunk_planes(MapState* st, int strand, uint32_t* lo, uint32_t* hi, uint32_t* nn, hipStream_t s,
+                        std::string* err) {
+  const size_t words = (size_t)search_chunk_words(st);
+  std::vector<uint2> pk(words);
+  MAP_TRY(hipStreamSynchronize(s));
+  MAP_TRY(hipMemcpy(pk.data(), st->search.pk[strand].p, sizeof(uint2) * words, hipMemcpyDeviceToHost));
+  MAP_TRY(hipMemcpy(nn, st->search.nm[strand].p, sizeof(uint32_t) * words, hipMemcpyDeviceToHost));
+  for (size_t w = 0; w < words; ++w) {
+    lo[w] = pk[w].x;
+    hi[w] = pk[w].y;
   }
   return 0;
 }

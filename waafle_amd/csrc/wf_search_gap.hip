@@ -172,13 +172,13 @@ int gapped_device(MapState* st, const std::vector<GapAnchor>& anchors, int band,
 
 }  // namespace
 
-int search_gapped_run(MapState* st, const char* seq, const int64_t* off, int64_t n_subjects, const SearchRule& rule,
+int search_gapped_run(MapState* st, const ChunkSource& src, const int64_t* off, int64_t n_subjects, const SearchRule& rule,
                       int band, int xdrop_gap, const SearchGapOut& out, int64_t* n, SearchStats* stats,
                       SearchGapStats* gstats, hipStream_t s, std::string* err) {
   *n = 0;
   *gstats = SearchGapStats{0, 0};
   std::vector<SearchRec> recs;
-  MAP_RC(search_records(st, seq, off, n_subjects, rule, &recs, stats, s, err));
+  MAP_RC(search_records(st, src, off, n_subjects, rule, &recs, stats, s, err));
   gstats->anchors = (int64_t)recs.size();
   if (recs.empty()) return 0;
   std::vector<GapAnchor> anchors(recs.size());

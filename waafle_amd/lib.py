@@ -135,6 +135,11 @@ class WfSearchSubjects(C.Structure):
     _fields_ = [("n_subjects", C.c_int64), ("seq", _P), ("off", _P)]
 
 
+class WfSearchPackedSubjects(C.Structure):
+    _fields_ = [("n_subjects", C.c_int64), ("off", _P), ("lo", _P), ("hi", _P), ("nn", _P),
+                ("n_words", C.c_int64), ("bit0", C.c_int32), ("_pad", C.c_int32)]
+
+
 class WfSearchResult(C.Structure):
     _fields_ = [("capacity", C.c_int64), ("n", C.c_int64), ("contig", _P), ("subject", _P),
                 ("minus", _P), ("qstart", _P), ("sstart", _P), ("length", _P), ("matches", _P),
@@ -201,6 +206,12 @@ SIGNATURES = {
                             C.POINTER(WfSearchResult)]),
     "wf_search_gapped": (C.c_int, [C.c_void_p, C.POINTER(WfSearchSubjects), C.POINTER(WfSearchParams),
                                    C.POINTER(WfSearchGapParams), C.POINTER(WfSearchGapResult)]),
+    "wf_search_packed": (C.c_int, [C.c_void_p, C.POINTER(WfSearchPackedSubjects), C.POINTER(WfSearchParams),
+                                   C.POINTER(WfSearchResult)]),
+    "wf_search_gapped_packed": (C.c_int, [C.c_void_p, C.POINTER(WfSearchPackedSubjects),
+                                          C.POINTER(WfSearchParams), C.POINTER(WfSearchGapParams),
+                                          C.POINTER(WfSearchGapResult)]),
+    "wf_search_chunk_planes": (C.c_int, [C.c_void_p, C.c_int, _P, _P, _P, C.c_int64]),
     "wf_search_mask": (C.c_int, [C.c_void_p, C.POINTER(WfDustParams), C.POINTER(WfDustResult)]),
     "wf_details_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "wf_details_read": (C.c_int, [C.c_void_p, C.POINTER(WfDetails)]),

@@ -4,6 +4,8 @@
     python -m waafle_amd.search contigs.fna genes.fna --searcher native [--seed-length 21 ...]
     python -m waafle_amd.search contigs.fna genes.fna --searcher native --gapped [--band 15 --xdrop-gap 30]
     python -m waafle_amd.search contigs.fna genes.fna --searcher native --dust [--dust-out masked.tsv]
+    python -m waafle_amd.makedb genes.fna --out genes.wfdb       (once per database)
+    python -m waafle_amd.search contigs.fna genes.wfdb --searcher native [...]
 
 `--searcher blastn` (the default) issues exactly the reference's blastn command.  `--searcher
 native` runs the seed-and-extend search of wf_search.hip on one MI355X (DESIGN.md §12 states
@@ -19,8 +21,14 @@ low-complexity stretches, by the published symmetric-DUST definition, give no se
 mask: extensions run through them); blastn masks its query so by default, this search only
 when asked, and agreement with NCBI dustmasker is not measured.
 
-Host side (this module): the streaming subject-FASTA reader, the calls into wf_search /
-wf_search_gapped, the ordering and --max-target-seqs step and the row writer.
+A database formatted once with `python -m waafle_amd.makedb` (a .wfdb file)
+holds the genes as the bit planes the kernels use: the search maps the file and hands slices
+of it to wf_search_packed / wf_search_gapped_packed, so no run parses the FASTA again and three
+eighths of the bytes go to the device.  The table is the same either way.
+
+Host side (this module): the streaming subject-FASTA reader, the reader of a packed database,
+the calls into wf_search / wf_search_gapped and their packed forms, the ordering and
+--max-target-seqs step and the row writer.
 """
 from __future__ import annotations
 
@@ -29,6 +37,7 @@ import ctypes as C
 import gzip
 import math
 import os
+import struct
 import sys
 
 import numpy as np
@@ -161,6 +170,68 @@ class Searcher:
             raise L.WaafleHipError(rc, self.so.wf_last_error(self.mapper.h).decode())
         return out
 
+    @staticmethod
+    def _packed_subjects(chunk, off):
+        return L.WfSearchPackedSubjects(n_subjects=len(off) - 1, off=L.ptr(off), lo=L.ptr(chunk.lo), hi=L.ptr(chunk.hi),
+                                        nn=L.ptr(chunk.nn), n_words=len(chunk.lo), bit0=int(chunk.bit0))
+
+    def search_packed_once(self, chunk, capacity, params=None):
+        """(return code, full record count, records written): one wf_search_packed call on a
+        chunk of a packed database (PackedChunk, or anything with off, bit0, lo, hi, nn)."""
+        off = np.ascontiguousarray(chunk.off, dtype=np.int64)
+        out = {f: np.zeros(capacity, dt) for f, dt in RECORD_FIELDS}
+        sb = self._packed_subjects(chunk, off)
+        r = L.WfSearchResult(capacity=capacity, **{f: L.ptr(out[f]) for f, _ in RECORD_FIELDS})
+        rc = self.so.wf_search_packed(self.mapper.h, C.byref(sb), C.byref(params or self.params), C.byref(r))
+        if rc == L.WF_OK:
+            for f in STAT_FIELDS:
+                self.stats[f] += getattr(r, f)
+        n = int(r.n)
+        return rc, n, {f: a[:min(n, capacity)] for f, a in out.items()}
+
+    def search_packed(self, chunk, params=None):
+        rc, n, out = self.search_packed_once(chunk, self.capacity, params)
+        if rc == L.WF_E_NOMEM:                              # the call is repeatable with more room
+            self.capacity = max(n, 2 * self.capacity)
+            rc, n, out = self.search_packed_once(chunk, self.capacity, params)
+        if rc != L.WF_OK:
+            raise L.WaafleHipError(rc, self.so.wf_last_error(self.mapper.h).decode())
+        return out
+
+    def search_gapped_packed_once(self, chunk, capacity, params=None, gap_params=None):
+        """(return code, full record count, records written): one wf_search_gapped_packed call."""
+        off = np.ascontiguousarray(chunk.off, dtype=np.int64)
+        out = {f: np.zeros(capacity, dt) for f, dt in GAP_RECORD_FIELDS}
+        sb = self._packed_subjects(chunk, off)
+        r = L.WfSearchGapResult(capacity=capacity, **{f: L.ptr(out[f]) for f, _ in GAP_RECORD_FIELDS})
+        rc = self.so.wf_search_gapped_packed(self.mapper.h, C.byref(sb), C.byref(params or self.params),
+                                             C.byref(gap_params or self.gap_params), C.byref(r))
+        if rc == L.WF_OK:
+            for f in GAP_STAT_FIELDS:
+                self.stats[f] += getattr(r, f)
+        n = int(r.n)
+        return rc, n, {f: a[:min(n, capacity)] for f, a in out.items()}
+
+    def search_gapped_packed(self, chunk, params=None, gap_params=None):
+        rc, n, out = self.search_gapped_packed_once(chunk, self.capacity, params, gap_params)
+        if rc == L.WF_E_NOMEM:                              # the call is repeatable with more room
+            self.capacity = max(n, 2 * self.capacity)
+            rc, n, out = self.search_gapped_packed_once(chunk, self.capacity, params, gap_params)
+        if rc != L.WF_OK:
+            raise L.WaafleHipError(rc, self.so.wf_last_error(self.mapper.h).decode())
+        return out
+
+    def chunk_planes(self, total, strand):
+        """wf_search_chunk_planes: (lo, hi, nn) of the store that the last search call left on
+        the device for its chunk of `total` bases, strand 0 or 1; (total + 31) // 32 + 2 words
+        each.  A diagnostic."""
+        words = (int(total) + 31) // 32 + 2
+        lo, hi, nn = (np.zeros(words, np.uint32) for _ in range(3))
+        rc = self.so.wf_search_chunk_planes(self.mapper.h, int(strand), L.ptr(lo), L.ptr(hi), L.ptr(nn), words)
+        if rc != L.WF_OK:
+            raise L.WaafleHipError(rc, self.so.wf_last_error(self.mapper.h).decode())
+        return lo, hi, nn
+
     def close(self):
         self.mapper.close()
 
@@ -171,10 +242,15 @@ class Searcher:
         self.close()
 
 
-def search_chunk(searcher, seq, off, gapped=False):
+def search_chunk(searcher, seq, off=None, gapped=False):
     """`Searcher.search` (gapped: `Searcher.search_gapped`); a chunk that is refused as too big
-    (WF_E_TOOBIG) is halved, down to one subject."""
+    (WF_E_TOOBIG) is halved, down to one subject.  seq a PackedChunk (off is then its own): the
+    packed calls, and the halves are cut from its database anew."""
+    packed = isinstance(seq, PackedChunk)
     try:
+        if packed:
+            off = seq.off
+            return searcher.search_gapped_packed(seq) if gapped else searcher.search_packed(seq)
         return searcher.search_gapped(seq, off) if gapped else searcher.search(seq, off)
     except L.WaafleHipError as exc:
         n = len(off) - 1
@@ -183,8 +259,12 @@ def search_chunk(searcher, seq, off, gapped=False):
         if n <= 1:
             raise SearchError("a single subject is too big to search: {}".format(exc.msg))
     h = n // 2
-    a = search_chunk(searcher, seq[:off[h]], off[:h + 1], gapped)
-    b = search_chunk(searcher, seq[off[h]:], off[h:] - off[h], gapped)
+    if packed:
+        a = search_chunk(searcher, seq.db.chunk(seq.first, seq.first + h), None, gapped)
+        b = search_chunk(searcher, seq.db.chunk(seq.first + h, seq.last), None, gapped)
+    else:
+        a = search_chunk(searcher, seq[:off[h]], off[:h + 1], gapped)
+        b = search_chunk(searcher, seq[off[h]:], off[h:] - off[h], gapped)
     b["subject"] = b["subject"] + np.int32(h)
     return {f: np.concatenate([a[f], b[f]]) for f in a}
 
@@ -214,6 +294,19 @@ def _open(path):
     return gzip.open(path, "rb") if str(path).endswith(".gz") else open(path, "rb")
 
 
+def subject_id(line):
+    """The id of a header line (with its '>'): up to the first whitespace, a WAAFLE header."""
+    words = line[1:].split()
+    sid = words[0].decode() if words else ""
+    if "|" not in sid:
+        raise SearchError("bad subject id header: {} (a WAAFLE header is id|taxon|...)".format(sid))
+    return sid
+
+
+def headless_error(path):
+    return SearchError("sequence before the first FASTA header in {}".format(path))
+
+
 def iter_subject_chunks(path, chunk_bases=CHUNK_BASES):
     """(ids, seq, off) per chunk, in file order: whole subjects, at most `chunk_bases` bases
     together (a longer subject is a chunk of its own).  ids: the header up to the first
@@ -241,16 +334,12 @@ def iter_subject_chunks(path, chunk_bases=CHUNK_BASES):
                     yield flush(len(ids) - 1)
                 if len(ids) == 1 and held >= chunk_bases:
                     yield flush(1)
-                words = line[1:].split()
-                sid = words[0].decode() if words else ""
-                if "|" not in sid:
-                    raise SearchError("bad subject id header: {} (a WAAFLE header is id|taxon|...)".format(sid))
-                ids.append(sid)
+                ids.append(subject_id(line))
                 parts.append([])
                 sizes.append(0)
             else:
                 if not ids:
-                    raise SearchError("sequence before the first FASTA header in {}".format(path))
+                    raise headless_error(path)
                 parts[-1].append(line)
                 sizes[-1] += len(line)
                 held += len(line)
@@ -258,6 +347,132 @@ def iter_subject_chunks(path, chunk_bases=CHUNK_BASES):
         yield flush(len(ids) - 1)
     if ids:
         yield flush(len(ids))
+
+
+# ---------------------------------------------------------------------------
+# the packed database (.wfdb, written by waafle_amd.makedb)
+# ---------------------------------------------------------------------------
+
+DB_MAGIC = b"WAAFLEDB"
+DB_VERSION = 1
+DB_ALIGN = 64
+DB_HEADER = struct.Struct("<8sIIqqqq")       # magic, version, 0, n_subjects, total, plane_words, id_bytes
+
+
+def db_align(n):
+    return -(-n // DB_ALIGN) * DB_ALIGN
+
+
+def db_sections(n, words, id_bytes):
+    """{section: (byte offset, items)} of a database of n subjects, and the file's length"""
+    at, out = DB_ALIGN, {}
+    for name, items, size in (("off", n + 1, 8), ("id_off", n + 1, 8), ("ids", id_bytes, 1), ("lo", words, 4),
+                              ("hi", words, 4), ("nn", words, 4)):
+        out[name] = (at, items)
+        at = db_align(at + items * size)
+    return out, at
+
+
+def is_packed_db(path):
+    try:
+        with open(path, "rb") as fh:
+            return fh.read(len(DB_MAGIC)) == DB_MAGIC
+    except OSError:
+        return False
+
+
+class PackedChunk:
+    """Subjects [first, last) of a PackedDb as the packed calls take them: `off` relative to
+    the chunk, and `lo`, `hi`, `nn`, views into the file's map, in which base i of the chunk
+    is bit (bit0 + i) & 31 of word (bit0 + i) >> 5."""
+
+    def __init__(self, db, first, last):
+        self.db, self.first, self.last = db, int(first), int(last)
+        start = int(db.off[first])
+        self.off = np.asarray(db.off[first:last + 1], np.int64) - start
+        self.bit0 = start & 31
+        w0, n_words = start >> 5, (self.bit0 + int(self.off[-1]) + 31) // 32
+        self.lo, self.hi, self.nn = (p[w0:w0 + n_words] for p in (db.lo, db.hi, db.nn))
+
+
+class _DbIds:
+    """The ids of a PackedDb as a read-only sequence, decoded when asked for."""
+
+    def __init__(self, id_off, blob):
+        self.id_off, self.blob = id_off, blob
+
+    def __len__(self):
+        return len(self.id_off) - 1
+
+    def __getitem__(self, g):
+        if isinstance(g, slice):
+            return [self[i] for i in range(*g.indices(len(self)))]
+        if g < 0:
+            g += len(self)
+        if not 0 <= g < len(self):
+            raise IndexError(g)
+        return bytes(self.blob[int(self.id_off[g]):int(self.id_off[g + 1])]).decode()
+
+    def __iter__(self):
+        return (self[g] for g in range(len(self)))
+
+
+class PackedDb:
+    """A .wfdb file, memory-mapped read-only: `off` [n + 1], `lens`, `ids`, and the planes
+    `lo`, `hi`, `nn`.  Opening it checks the header, every size against the file's length and
+    the offsets; what fails is a SearchError."""
+
+    def __init__(self, path):
+        self.path = str(path)
+        size = os.path.getsize(self.path)
+        if size < DB_ALIGN:
+            raise SearchError("{}: not a packed database ({} bytes)".format(path, size))
+        with open(self.path, "rb") as fh:
+            magic, version, _, n, total, words, id_bytes = DB_HEADER.unpack(fh.read(DB_HEADER.size))
+        if magic != DB_MAGIC:
+            raise SearchError("{}: not a packed database (bad magic)".format(path))
+        if version != DB_VERSION:
+            raise SearchError("{}: packed database version {} (this reader knows version {}): format it again "
+                              "with `python -m waafle_amd.makedb`".format(path, version, DB_VERSION))
+        if n < 0 or total < 0 or id_bytes < 0 or n >= 1 << 40 or id_bytes >= 1 << 50 or total >= 1 << 50 or \
+                words != (total + 31) // 32 + 2:
+            raise SearchError("{}: inconsistent header (subjects {}, bases {}, plane words {}, id bytes {})".format(
+                path, n, total, words, id_bytes))
+        sec, length = db_sections(n, words, id_bytes)
+        if size != length:
+            raise SearchError("{}: {} bytes, but its header describes {} (truncated or corrupt)".format(
+                path, size, length))
+        self.n_subjects, self.total, self.words = n, total, words
+        mm = np.memmap(self.path, dtype=np.uint8, mode="r")
+
+        def view(name, dtype):
+            at, items = sec[name]
+            return mm[at:at + items * np.dtype(dtype).itemsize].view(dtype)
+
+        self.off, id_off = view("off", "<i8"), view("id_off", "<i8")
+        for what, a, end in (("subject", self.off, total), ("id", id_off, id_bytes)):
+            if a[0] != 0 or a[-1] != end or (n and bool((np.diff(a) < 0).any())):
+                raise SearchError("{}: bad {} offsets (they must start at 0, not decrease and end at {})".format(
+                    path, what, end))
+        self.ids = _DbIds(id_off, view("ids", np.uint8))
+        self.lens = np.diff(self.off)
+        self.lo, self.hi, self.nn = view("lo", "<u4"), view("hi", "<u4"), view("nn", "<u4")
+
+    def chunk(self, first, last):
+        return PackedChunk(self, first, last)
+
+    def chunks(self, chunk_bases=CHUNK_BASES):
+        """PackedChunks in file order, cut where iter_subject_chunks cuts the FASTA: whole
+        subjects, at most `chunk_bases` bases together; a subject of that many or more is a
+        chunk of its own."""
+        off, n, first = self.off, self.n_subjects, 0
+        while first < n:
+            if off[first + 1] - off[first] >= chunk_bases:
+                last = first + 1
+            else:                                            # the last subject that still fits: past first
+                last = min(int(np.searchsorted(off, off[first] + chunk_bases, side="right")) - 1, n)
+            yield self.chunk(first, last)
+            first = last
 
 
 # ---------------------------------------------------------------------------
@@ -337,7 +552,8 @@ def format_rows(rec, order, contig_names, contig_lens, subject_ids, subject_lens
 def search_files(query, db, out_path, device=0, chunk_bases=CHUNK_BASES, max_target_seqs=MAX_TARGET_SEQS,
                  say=lambda *a: None, gapped=False, band=15, xdrop_gap=30, dust=False, dust_window=64,
                  dust_level=20, dust_out=None, **params):
-    """The native search of the FASTA `db` against the contigs `query`, written to `out_path`;
+    """The native search of `db`, a genes' FASTA or a packed database (makedb: told by its
+    magic), against the contigs `query`, written to `out_path`;
     gapped: the alignments of the gapped extension in place of the ungapped HSPs; dust: seeds
     from the contigs' unmasked S-mers only, and with dust_out the masked intervals written there.
     Returns the searcher's counters plus rows, subjects and database bases."""
@@ -352,18 +568,24 @@ def search_files(query, db, out_path, device=0, chunk_bases=CHUNK_BASES, max_tar
             if dust_out:
                 with open(dust_out, "w") as fh:
                     fh.write("".join(r + "\n" for r in format_mask_rows(mask_intervals(s.mask(), off), names)))
-        for cid, cseq, coff in iter_subject_chunks(db, chunk_bases):
-            rec = search_chunk(s, cseq, coff, gapped)
+        pdb = PackedDb(db) if is_packed_db(db) else None
+        for item in (pdb.chunks(chunk_bases) if pdb else iter_subject_chunks(db, chunk_bases)):
+            if pdb:
+                cid, coff = range(item.first, item.last), item.off
+                rec = search_chunk(s, item, None, gapped)
+            else:
+                cid, cseq, coff = item
+                rec = search_chunk(s, cseq, coff, gapped)
             rec["subject"] = rec["subject"] + np.int32(len(ids))
             parts.append(rec)
-            ids += cid
+            ids += cid                                       # a packed database: its subjects' numbers
             lens.append(np.diff(coff))
             say("  {:,} subjects searched, {:,} records".format(len(ids), sum(len(p["contig"]) for p in parts)))
         stats = dict(s.stats)
     rec = {f: np.concatenate([p[f] for p in parts]) if parts else np.zeros(0, dt) for f, dt in fields}
     lens = np.concatenate(lens) if lens else np.zeros(0, np.int64)
     order = order_records(rec, max_target_seqs)
-    rows = format_rows(rec, order, names, np.diff(off), ids, lens, int(lens.sum()))
+    rows = format_rows(rec, order, names, np.diff(off), pdb.ids if pdb else ids, lens, int(lens.sum()))
     with open(out_path, "w") as fh:
         fh.write("".join(r + "\n" for r in rows))
     stats.update(rows=len(rows), subjects=len(ids), db_bases=int(lens.sum()))
@@ -382,9 +604,12 @@ def build_parser():
         formatter_class=argparse.RawTextHelpFormatter)
     ap.add_argument("query", help="contigs file (fasta format)")
     ap.add_argument("db", help="path to WAAFLE BLAST database; with --searcher native: the genes' FASTA\n"
-                               "file (plain or .gz) with WAAFLE headers (id|taxon|system=name...).  The\n"
-                               "binary files of a BLAST database cannot be read: get the FASTA with\n"
-                               "`blastdbcmd -db <db> -entry all`")
+                               "file (plain or .gz) with WAAFLE headers (id|taxon|system=name...), or the\n"
+                               ".wfdb file that `python -m waafle_amd.makedb genes.fna --out genes.wfdb`\n"
+                               "makes of it once: the genes as bit planes, which a search maps and sends\n"
+                               "to the GPU as they are (no FASTA parsing per run, 3/8 of the bytes; the\n"
+                               "same table).  The binary files of a BLAST database cannot be read: get\n"
+                               "the FASTA with `blastdbcmd -db <db> -entry all`")
     ap.add_argument("--blastn", default="blastn", metavar="<path>", help="path to blastn binary\n[default: $PATH]")
     ap.add_argument("--threads", default="1", metavar="<int>",
                     help="number of CPU cores to use in blastn search\n[default: 1]")
