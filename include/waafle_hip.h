@@ -33,7 +33,8 @@ extern "C" {
                                     still 6 (additive): wf_search, wf_search_gapped;
                                     still 6 (additive): wf_search_mask;
                                     still 6 (additive): wf_search_packed, wf_search_gapped_packed,
-                                                        wf_search_chunk_planes */
+                                                        wf_search_chunk_planes;
+                                    still 6 (additive): wf_hits_from_records */
 
 enum wf_status {
   WF_OK = 0,
@@ -552,6 +553,71 @@ typedef struct wf_dust_result {
 /* WF_E_STATE before wf_map_index; WF_E_BADINPUT for window outside 8..64 or level < 1.
    Returns after the work is done. */
 int wf_search_mask(wf_ctx* ctx, const wf_dust_params* params, wf_dust_result* out);
+
+/* ---- search records -> hit arrays ---------------------------------------
+ * The hit arrays of wf_batch / wf_gc_batch from the search's records, without the table: bit
+ * for bit what inputs.load_inputs gives for the table search.format_rows writes of the same
+ * records.  The records come in the table's order (search.order_records), so sorted by contig;
+ * an ungapped record (wf_search_result) has qspan = sspan = length.  Per record:
+ *   hit_qlo = qstart + 1, hit_qhi = qstart + qspan; s0 = sstart + 1, s1 = sstart + sspan (on
+ *   either strand: a minus row's subject coordinates mirror back to these);
+ *   ltrim = max(0, s0 - hit_qlo), rtrim = max(0, slen - s0 - qlen + hit_qlo);
+ *   hit_scov = (double)(s1 - s0 + 1) / (double)(slen - ltrim - rtrim);
+ *   pident = n / 1000.0, n the integer nearest to x * 1000 exactly, ties to even, for the double
+ *   x = (100.0 * matches) / length: the value of the text "%.3f" % x;
+ *   hit_score = hit_scov * pident / 100.0 (two roundings); hit_taxon and hit_sysmask gathered by
+ *   subject; hit_strand = minus; hit_key as wf_pack_hit_keys packs it for min_scov;
+ *   hit_off[c] = records with contig < c. */
+typedef struct wf_hit_records {   /* host memory, [n] each */
+  int64_t n;                      /* < 2^31 */
+  const int32_t* contig;          /* not decreasing */
+  const int32_t* subject;         /* index into the subject tables */
+  const uint8_t* minus;           /* 0 / 1 */
+  const int32_t* qstart;          /* 0-based first contig base */
+  const int32_t* qspan;
+  const int32_t* sstart;          /* 0-based, on the variant */
+  const int32_t* sspan;
+  const int32_t* length;          /* alignment columns */
+  const int32_t* matches;
+} wf_hit_records;
+
+typedef struct wf_hit_tables {    /* host memory */
+  int32_t n_contigs;
+  int32_t n_subjects;
+  const int64_t* qlen;            /* [n_contigs] contig lengths */
+  const int64_t* slen;            /* [n_subjects] subject lengths */
+  const int32_t* subject_taxon;   /* [n_subjects] interned taxon id, 0 .. 2^24 - 1 */
+  const uint32_t* subject_sysmask;/* [n_subjects] annotation systems present */
+  double min_scov;                /* read for bit 24 of hit_key only */
+} wf_hit_tables;
+
+typedef struct wf_hits_out {      /* the arrays wf_batch and wf_gc_batch take */
+  int32_t device_resident;        /* 1: device pointers, the call only enqueues on the context
+                                     stream (the records and tables must stay valid until
+                                     wf_synchronize, or a later synchronising call, returns);
+                                     0: host arrays, copied out and synchronised */
+  int32_t _pad;
+  int64_t* hit_off;               /* [n_contigs + 1] */
+  int32_t* hit_qlo;               /* [n] each from here */
+  int32_t* hit_qhi;
+  int32_t* hit_taxon;
+  int8_t* hit_strand;
+  double* hit_score;
+  double* hit_scov;
+  uint32_t* hit_sysmask;
+  uint32_t* hit_key;
+} wf_hits_out;
+
+/* WF_E_BADINPUT, checked on the host before anything is launched or written, so the outputs are
+   untouched: a null struct, a null hit_off, a null record or output array with n > 0 or a null
+   table a record needs, n or a table size negative, n >= 2^31; and, named by its first record in
+   wf_last_error: a contig or subject outside its table, a contig column that decreases, minus
+   above 1, length <= 0, matches < 0 or > length, qspan or sspan <= 0, qlen or slen <= 0 (of a
+   contig or subject some record names), a denominator slen - ltrim - rtrim <= 0, hit_qlo or
+   hit_qhi outside int32, a taxon outside 24 bits.  n = 0 and n_contigs = 0 are valid (hit_off is
+   still written). */
+int wf_hits_from_records(wf_ctx* ctx, const wf_hit_records* records, const wf_hit_tables* tables,
+                         wf_hits_out* out);
 
 /* ---- --write-details (orgscorer.py:766-812, 931-937) --------------------------------
  * With details on, the next wf_score (staged mode) also records, for every roll-up level,

@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <cstdarg>
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -32,6 +33,10 @@ struct wf_ctx {
   DevBuf jn_site_off, jn_loc_off, jn_loc_contig, jn_lstart, jn_lend, jn_pc, jn_m1s, jn_m1e, jn_m2s, jn_m2e;
   DevBuf jn_diff, jn_cov, jn_prefix, jn_hits, jn_lhits, jn_c1, jn_c2, jn_cj, jn_ratio, jn_tmp;
   DevBuf jn_pfirst, jn_pmask;
+  // wf_hits_from_records staging: the record columns, the tables, and host-resident outputs
+  DevBuf hr_contig, hr_subject, hr_minus, hr_qstart, hr_qspan, hr_sstart, hr_sspan, hr_length, hr_matches;
+  DevBuf ht_qlen, ht_slen, ht_taxon, ht_sysmask;
+  DevBuf ho_off, ho_qlo, ho_qhi, ho_taxon, ho_strand, ho_score, ho_scov, ho_sysmask, ho_key;
   bool have_lin = false;
   int64_t lds_bytes = 24 * 1024;   // decision arena per workgroup (wf_set_lds_bytes)
   // staging for host-resident batches
@@ -219,6 +224,11 @@ void wf_free(wf_ctx* ctx) {
                     &ctx->jn_m2e, &ctx->jn_diff, &ctx->jn_cov, &ctx->jn_prefix, &ctx->jn_hits,
                     &ctx->jn_lhits, &ctx->jn_c1, &ctx->jn_c2, &ctx->jn_cj, &ctx->jn_ratio,
                     &ctx->jn_tmp, &ctx->jn_pfirst, &ctx->jn_pmask,
+                    &ctx->hr_contig, &ctx->hr_subject, &ctx->hr_minus, &ctx->hr_qstart, &ctx->hr_qspan,
+                    &ctx->hr_sstart, &ctx->hr_sspan, &ctx->hr_length, &ctx->hr_matches, &ctx->ht_qlen,
+                    &ctx->ht_slen, &ctx->ht_taxon, &ctx->ht_sysmask, &ctx->ho_off, &ctx->ho_qlo, &ctx->ho_qhi,
+                    &ctx->ho_taxon, &ctx->ho_strand, &ctx->ho_score, &ctx->ho_scov, &ctx->ho_sysmask,
+                    &ctx->ho_key,
                     &ctx->b_hit_off, &ctx->b_qlo, &ctx->b_qhi, &ctx->b_taxon, &ctx->b_hstrand,
                     &ctx->b_score, &ctx->b_scov, &ctx->b_sysmask, &ctx->b_hkey, &ctx->b_loc_off,
                     &ctx->b_lstart, &ctx->b_lend, &ctx->b_lstrand, &ctx->r_call, &ctx->r_crit,
@@ -580,6 +590,102 @@ int wf_genecall(wf_ctx* ctx, const wf_gc_batch* b, const wf_gc_params* p, wf_gc_
     if (status[g] != 0)
       return fail(ctx, WF_E_NOMEM, "contig group %lld has more than %lld intervals", (long long)g,
                   (long long)kCapMax);
+  return WF_OK;
+}
+
+// The checks of wf_hits_from_records (include/waafle_hip.h), all before any launch: after them
+// the kernels index and divide with checked values only.
+static int check_hit_records(wf_ctx* ctx, const wf_hit_records* rc, const wf_hit_tables* t, const wf_hits_out* o) {
+  if (!rc || !t || !o) return fail(ctx, WF_E_BADINPUT, "null records/tables/out");
+  const int64_t n = rc->n;
+  if (n < 0 || t->n_contigs < 0 || t->n_subjects < 0) return fail(ctx, WF_E_BADINPUT, "negative sizes");
+  if (n >= (int64_t)1 << 31) return fail(ctx, WF_E_BADINPUT, "n must be < 2^31");
+  if (!o->hit_off) return fail(ctx, WF_E_BADINPUT, "null hit_off");
+  if (n == 0) return WF_OK;
+  if (!rc->contig || !rc->subject || !rc->minus || !rc->qstart || !rc->qspan || !rc->sstart || !rc->sspan ||
+      !rc->length || !rc->matches)
+    return fail(ctx, WF_E_BADINPUT, "null record arrays");
+  if (!t->qlen || !t->slen || !t->subject_taxon || !t->subject_sysmask) return fail(ctx, WF_E_BADINPUT, "null tables");
+  if (!o->hit_qlo || !o->hit_qhi || !o->hit_taxon || !o->hit_strand || !o->hit_score || !o->hit_scov ||
+      !o->hit_sysmask || !o->hit_key)
+    return fail(ctx, WF_E_BADINPUT, "null output arrays");
+  for (int64_t i = 0; i < n; ++i) {
+    const long long r = (long long)i;
+    const int32_t c = rc->contig[i], g = rc->subject[i];
+    if (c < 0 || c >= t->n_contigs) return fail(ctx, WF_E_BADINPUT, "record %lld: contig %d outside its table", r, c);
+    if (g < 0 || g >= t->n_subjects) return fail(ctx, WF_E_BADINPUT, "record %lld: subject %d outside its table", r, g);
+    if (i > 0 && c < rc->contig[i - 1]) return fail(ctx, WF_E_BADINPUT, "record %lld: the contig column decreases", r);
+    if (rc->minus[i] > 1) return fail(ctx, WF_E_BADINPUT, "record %lld: minus is %d", r, (int)rc->minus[i]);
+    if (rc->length[i] <= 0) return fail(ctx, WF_E_BADINPUT, "record %lld: length %d", r, rc->length[i]);
+    if (rc->matches[i] < 0 || rc->matches[i] > rc->length[i])
+      return fail(ctx, WF_E_BADINPUT, "record %lld: matches %d of length %d", r, rc->matches[i], rc->length[i]);
+    if (rc->qspan[i] <= 0 || rc->sspan[i] <= 0)
+      return fail(ctx, WF_E_BADINPUT, "record %lld: qspan %d, sspan %d", r, rc->qspan[i], rc->sspan[i]);
+    const int64_t qlen = t->qlen[c], slen = t->slen[g];
+    if (qlen <= 0 || slen <= 0)
+      return fail(ctx, WF_E_BADINPUT, "record %lld: qlen %lld, slen %lld", r, (long long)qlen, (long long)slen);
+    const int64_t q1 = (int64_t)rc->qstart[i] + 1, qhi = (int64_t)rc->qstart[i] + rc->qspan[i];
+    if (q1 < INT32_MIN || q1 > INT32_MAX || qhi > INT32_MAX)
+      return fail(ctx, WF_E_BADINPUT, "record %lld: query interval outside int32", r);
+    const int64_t s0 = (int64_t)rc->sstart[i] + 1;
+    const int64_t ltrim = std::max<int64_t>(0, s0 - q1), rtrim = std::max<int64_t>(0, slen - s0 - qlen + q1);
+    if (slen - ltrim - rtrim <= 0)
+      return fail(ctx, WF_E_BADINPUT, "record %lld: scov denominator %lld", r, (long long)(slen - ltrim - rtrim));
+    const int32_t taxon = t->subject_taxon[g];
+    if (taxon < 0 || taxon >= (1 << 24)) return fail(ctx, WF_E_BADINPUT, "record %lld: taxon %d outside 24 bits", r, taxon);
+  }
+  return WF_OK;
+}
+
+int wf_hits_from_records(wf_ctx* ctx, const wf_hit_records* rc, const wf_hit_tables* t, wf_hits_out* o) {
+  if (!ctx) return WF_E_BADINPUT;
+  int rv = check_hit_records(ctx, rc, t, o);
+  if (rv) return rv;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const int64_t n = rc->n, N = t->n_contigs, G = n > 0 ? t->n_subjects : 0;
+  wf::HitsArgs a{};
+  a.n = n;
+  a.n_contigs = t->n_contigs;
+  a.min_scov = t->min_scov;
+  if ((rv = upload(ctx, ctx->hr_contig, rc->contig, n, &a.contig)) ||
+      (rv = upload(ctx, ctx->hr_subject, rc->subject, n, &a.subject)) ||
+      (rv = upload(ctx, ctx->hr_minus, rc->minus, n, &a.minus)) ||
+      (rv = upload(ctx, ctx->hr_qstart, rc->qstart, n, &a.qstart)) ||
+      (rv = upload(ctx, ctx->hr_qspan, rc->qspan, n, &a.qspan)) ||
+      (rv = upload(ctx, ctx->hr_sstart, rc->sstart, n, &a.sstart)) ||
+      (rv = upload(ctx, ctx->hr_sspan, rc->sspan, n, &a.sspan)) ||
+      (rv = upload(ctx, ctx->hr_length, rc->length, n, &a.length)) ||
+      (rv = upload(ctx, ctx->hr_matches, rc->matches, n, &a.matches)) ||
+      (rv = upload(ctx, ctx->ht_qlen, t->qlen, n > 0 ? N : 0, &a.qlen)) ||
+      (rv = upload(ctx, ctx->ht_slen, t->slen, G, &a.slen)) ||
+      (rv = upload(ctx, ctx->ht_taxon, t->subject_taxon, G, &a.subject_taxon)) ||
+      (rv = upload(ctx, ctx->ht_sysmask, t->subject_sysmask, G, &a.subject_sysmask)))
+    return rv;
+  if (o->device_resident) {
+    a.hit_off = o->hit_off; a.hit_qlo = o->hit_qlo; a.hit_qhi = o->hit_qhi; a.hit_taxon = o->hit_taxon;
+    a.hit_strand = o->hit_strand; a.hit_score = o->hit_score; a.hit_scov = o->hit_scov;
+    a.hit_sysmask = o->hit_sysmask; a.hit_key = o->hit_key;
+  } else if ((rv = alloc_out(ctx, ctx->ho_off, N + 1, &a.hit_off)) ||
+             (rv = alloc_out(ctx, ctx->ho_qlo, n, &a.hit_qlo)) || (rv = alloc_out(ctx, ctx->ho_qhi, n, &a.hit_qhi)) ||
+             (rv = alloc_out(ctx, ctx->ho_taxon, n, &a.hit_taxon)) ||
+             (rv = alloc_out(ctx, ctx->ho_strand, n, &a.hit_strand)) ||
+             (rv = alloc_out(ctx, ctx->ho_score, n, &a.hit_score)) ||
+             (rv = alloc_out(ctx, ctx->ho_scov, n, &a.hit_scov)) ||
+             (rv = alloc_out(ctx, ctx->ho_sysmask, n, &a.hit_sysmask)) ||
+             (rv = alloc_out(ctx, ctx->ho_key, n, &a.hit_key))) {
+    return rv;
+  }
+  HIP_TRY(ctx, wf::launch_hits(a, ctx->stream));
+  // enqueued only: the records and tables stay the caller's until the stream has passed the
+  // uploads (wf_synchronize), the outputs are ready in stream order
+  if (o->device_resident) return WF_OK;
+  if ((rv = download(ctx, o->hit_off, a.hit_off, N + 1)) || (rv = download(ctx, o->hit_qlo, a.hit_qlo, n)) ||
+      (rv = download(ctx, o->hit_qhi, a.hit_qhi, n)) || (rv = download(ctx, o->hit_taxon, a.hit_taxon, n)) ||
+      (rv = download(ctx, o->hit_strand, a.hit_strand, n)) || (rv = download(ctx, o->hit_score, a.hit_score, n)) ||
+      (rv = download(ctx, o->hit_scov, a.hit_scov, n)) || (rv = download(ctx, o->hit_sysmask, a.hit_sysmask, n)) ||
+      (rv = download(ctx, o->hit_key, a.hit_key, n)))
+    return rv;
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return WF_OK;
 }
 

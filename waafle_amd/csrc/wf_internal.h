@@ -243,6 +243,20 @@ struct DustStats { int64_t masked_bases, kmers_before, kmers_after; };
 int dust_mask(MapState* st, int window, int level, DustStats* stats, uint32_t* host_mask, hipStream_t s,
               std::string* err);
 
+// search records -> hit arrays (wf_hits.hip).  Device pointers; every index and
+// divisor checked by the caller (wf_hits_from_records) before the launch.
+struct HitsArgs {
+  int64_t n;                               // records
+  int32_t n_contigs;
+  double min_scov;                         // bit 24 of hit_key
+  const int32_t* contig; const int32_t* subject; const uint8_t* minus; const int32_t* qstart; const int32_t* qspan;
+  const int32_t* sstart; const int32_t* sspan; const int32_t* length; const int32_t* matches;
+  const int64_t* qlen; const int64_t* slen; const int32_t* subject_taxon; const uint32_t* subject_sysmask;
+  int64_t* hit_off; int32_t* hit_qlo; int32_t* hit_qhi; int32_t* hit_taxon; int8_t* hit_strand; double* hit_score;
+  double* hit_scov; uint32_t* hit_sysmask; uint32_t* hit_key;
+};
+hipError_t launch_hits(const HitsArgs& a, hipStream_t s);
+
 // --write-details: per roll-up level, the evaluated (active) contigs and the segment
 // records of the level, copied to the host (wf_staged.hip details_level)
 struct DetailsLevel {

@@ -167,6 +167,22 @@ class WfDustResult(C.Structure):
                 ("kmers_after", C.c_int64)]
 
 
+class WfHitRecords(C.Structure):
+    _fields_ = [("n", C.c_int64), ("contig", _P), ("subject", _P), ("minus", _P), ("qstart", _P),
+                ("qspan", _P), ("sstart", _P), ("sspan", _P), ("length", _P), ("matches", _P)]
+
+
+class WfHitTables(C.Structure):
+    _fields_ = [("n_contigs", C.c_int32), ("n_subjects", C.c_int32), ("qlen", _P), ("slen", _P),
+                ("subject_taxon", _P), ("subject_sysmask", _P), ("min_scov", C.c_double)]
+
+
+class WfHitsOut(C.Structure):
+    _fields_ = [("device_resident", C.c_int32), ("_pad", C.c_int32), ("hit_off", _P), ("hit_qlo", _P),
+                ("hit_qhi", _P), ("hit_taxon", _P), ("hit_strand", _P), ("hit_score", _P), ("hit_scov", _P),
+                ("hit_sysmask", _P), ("hit_key", _P)]
+
+
 class WfDetails(C.Structure):
     _fields_ = [("n_evals", C.c_int64), ("eval_contig", _P), ("eval_level", _P),
                 ("n_segs", C.c_int64), ("seg_level", _P), ("seg_contig", _P), ("seg_clade", _P),
@@ -213,6 +229,8 @@ SIGNATURES = {
                                           C.POINTER(WfSearchGapResult)]),
     "wf_search_chunk_planes": (C.c_int, [C.c_void_p, C.c_int, _P, _P, _P, C.c_int64]),
     "wf_search_mask": (C.c_int, [C.c_void_p, C.POINTER(WfDustParams), C.POINTER(WfDustResult)]),
+    "wf_hits_from_records": (C.c_int, [C.c_void_p, C.POINTER(WfHitRecords), C.POINTER(WfHitTables),
+                                       C.POINTER(WfHitsOut)]),
     "wf_details_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "wf_details_read": (C.c_int, [C.c_void_p, C.POINTER(WfDetails)]),
 }

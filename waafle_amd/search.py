@@ -519,6 +519,15 @@ def bitscore_text(score):
     return str(int(bits)) if bits > 99.9 else "%.1f" % bits
 
 
+def evalue(qlen, db_bases, score):
+    """K qlen D exp(-LAMBDA score); infinite where exp overflows (a score below about -550, which
+    no search reports: records made by hand)."""
+    try:
+        return K * qlen * db_bases * math.exp(-LAMBDA * score)
+    except OverflowError:
+        return math.inf
+
+
 def format_rows(rec, order, contig_names, contig_lens, subject_ids, subject_lens, db_bases):
     """The 15 columns of utils.c_blast_fields, tab-separated, 1-based; a minus HSP has
     descending subject coordinates.  evalue = K qlen D exp(-LAMBDA score), D the database's
@@ -531,7 +540,7 @@ def format_rows(rec, order, contig_names, contig_lens, subject_ids, subject_lens
         for c, g, minus, qs, qn, ss, sn, length, m, gaps in zip(*cols):
             score, M, qlen = (6 * m - 4 * length - gaps) / 2, int(subject_lens[g]), int(contig_lens[c])
             s0, s1 = (M - ss, M - ss - sn + 1) if minus else (ss + 1, ss + sn)
-            ev = K * qlen * db_bases * math.exp(-LAMBDA * score)
+            ev = evalue(qlen, db_bases, score)
             out.append("\t".join(str(v) for v in (
                 contig_names[c], subject_ids[g], qlen, M, length, qs + 1, qs + qn, s0, s1,
                 "%.3f" % (100.0 * m / length), m, gaps, "%.2e" % ev, bitscore_text(score),
@@ -541,7 +550,7 @@ def format_rows(rec, order, contig_names, contig_lens, subject_ids, subject_lens
     for c, g, minus, qs, ss, length, m in zip(*cols):
         score, M, qlen = 3 * m - 2 * length, int(subject_lens[g]), int(contig_lens[c])
         s0, s1 = (M - ss, M - ss - length + 1) if minus else (ss + 1, ss + length)
-        ev = K * qlen * db_bases * math.exp(-LAMBDA * score)
+        ev = evalue(qlen, db_bases, score)
         out.append("\t".join(str(v) for v in (
             contig_names[c], subject_ids[g], qlen, M, length, qs + 1, qs + length, s0, s1,
             "%.3f" % (100.0 * m / length), m, 0, "%.2e" % ev, bitscore_text(score),
@@ -557,8 +566,25 @@ def search_files(query, db, out_path, device=0, chunk_bases=CHUNK_BASES, max_tar
     gapped: the alignments of the gapped extension in place of the ungapped HSPs; dust: seeds
     from the contigs' unmasked S-mers only, and with dust_out the masked intervals written there.
     Returns the searcher's counters plus rows, subjects and database bases."""
-    fields = GAP_RECORD_FIELDS if gapped else RECORD_FIELDS
     names, seq, off = mapper.read_fasta(query)
+    rec, ids, lens, stats = search_records(names, seq, off, db, device=device, chunk_bases=chunk_bases, say=say,
+                                           gapped=gapped, band=band, xdrop_gap=xdrop_gap, dust=dust,
+                                           dust_window=dust_window, dust_level=dust_level, dust_out=dust_out, **params)
+    order = order_records(rec, max_target_seqs)
+    rows = format_rows(rec, order, names, np.diff(off), ids, lens, int(lens.sum()))
+    with open(out_path, "w") as fh:
+        fh.write("".join(r + "\n" for r in rows))
+    stats.update(rows=len(rows), subjects=len(ids), db_bases=int(lens.sum()))
+    return stats
+
+
+def search_records(names, seq, off, db, device=0, chunk_bases=CHUNK_BASES, say=lambda *a: None, gapped=False, band=15,
+                   xdrop_gap=30, dust=False, dust_window=64, dust_level=20, dust_out=None, **params):
+    """The search of search_files, up to its records: `db` chunk by chunk against the contigs
+    (names, seq, off as mapper.read_fasta gives them).  Returns (records with database-wide
+    subject numbers, in the order found; the subjects' ids; their lengths; the searcher's
+    counters)."""
+    fields = GAP_RECORD_FIELDS if gapped else RECORD_FIELDS
     ids, lens, parts = [], [], []
     with Searcher(seq, off, device=device, band=band, xdrop_gap=xdrop_gap, dust=dust, dust_window=dust_window,
                   dust_level=dust_level, **params) as s:
@@ -584,12 +610,7 @@ def search_files(query, db, out_path, device=0, chunk_bases=CHUNK_BASES, max_tar
         stats = dict(s.stats)
     rec = {f: np.concatenate([p[f] for p in parts]) if parts else np.zeros(0, dt) for f, dt in fields}
     lens = np.concatenate(lens) if lens else np.zeros(0, np.int64)
-    order = order_records(rec, max_target_seqs)
-    rows = format_rows(rec, order, names, np.diff(off), pdb.ids if pdb else ids, lens, int(lens.sum()))
-    with open(out_path, "w") as fh:
-        fh.write("".join(r + "\n" for r in rows))
-    stats.update(rows=len(rows), subjects=len(ids), db_bases=int(lens.sum()))
-    return stats
+    return rec, (pdb.ids if pdb else ids), lens, stats
 
 
 # ---------------------------------------------------------------------------
