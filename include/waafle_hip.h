@@ -34,7 +34,8 @@ extern "C" {
                                     still 6 (additive): wf_search_mask;
                                     still 6 (additive): wf_search_packed, wf_search_gapped_packed,
                                                         wf_search_chunk_planes;
-                                    still 6 (additive): wf_hits_from_records */
+                                    still 6 (additive): wf_hits_from_records;
+                                    still 6 (additive): wf_order_records */
 
 enum wf_status {
   WF_OK = 0,
@@ -618,6 +619,56 @@ typedef struct wf_hits_out {      /* the arrays wf_batch and wf_gc_batch take */
    still written). */
 int wf_hits_from_records(wf_ctx* ctx, const wf_hit_records* records, const wf_hit_tables* tables,
                          wf_hits_out* out);
+
+/* ---- the table's order and --max-target-seqs (search.order_records) -------
+ * Which of the search's records the table holds, and in which order.  The score, in 64 bits, is
+ * 3 matches - 2 length for ungapped records (qspan, sspan and gaps all null) and
+ * 6 matches - 4 length - gaps for gapped ones.  best of a (contig, subject) pair: the greatest
+ * score of its records.  Within a contig the pairs are ranked by (-best, subject), and the pairs
+ * of rank >= max_target_seqs lose their records.  The others go by (contig, -score, subject,
+ * minus, qstart, sstart), gapped records then by (qspan, sspan); records equal in all of these by
+ * their position in the input.  order[k] is the input index of the k-th record of the table. */
+typedef struct wf_order_in {      /* host memory, [n] each; the records in any order */
+  int64_t n;                      /* < 2^31 */
+  int64_t max_target_seqs;        /* >= 1 */
+  const int32_t* contig;          /* >= 0 */
+  const int32_t* subject;         /* >= 0 */
+  const uint8_t* minus;           /* 0 / 1 */
+  const int32_t* qstart;
+  const int32_t* sstart;
+  const int32_t* length;
+  const int32_t* matches;
+  const int32_t* qspan;           /* these three: all null (ungapped) or all given (gapped) */
+  const int32_t* sspan;
+  const int32_t* gaps;
+} wf_order_in;
+
+typedef struct wf_order_out {     /* host memory */
+  int64_t n_kept;                 /* written by the call */
+  int64_t* order;                 /* room for n; [0, n_kept) written */
+  /* the columns of wf_hit_records gathered in that order (an ungapped record has qspan = sspan =
+     length): each null (not wanted) or room for n, [0, n_kept) written */
+  int32_t* contig;
+  int32_t* subject;
+  uint8_t* minus;
+  int32_t* qstart;
+  int32_t* qspan;
+  int32_t* sstart;
+  int32_t* sspan;
+  int32_t* length;
+  int32_t* matches;
+} wf_order_out;
+
+/* Returns after the work is done.  n = 0 is valid (n_kept = 0).  WF_E_BADINPUT, checked on the
+   host before anything is uploaded or launched, so nothing is written: a null struct, a null
+   record column or a null order with n > 0, n < 0 or >= 2^31, max_target_seqs < 1, only some of
+   qspan / sspan / gaps given; and, named by its first record in wf_last_error: a contig or
+   subject < 0, minus above 1.  WF_E_NOMEM, also with nothing written, when device memory cannot
+   be had: the call holds 25 bytes per record of input (37 gapped), 8 per 64 bits of sort key
+   (the fields' ranges in this call decide: 8 to 32), 68 of sort and ranking arrays and, with any
+   column asked for, 33 of gathered columns: at most 170 bytes per record, plus the radix sort's
+   scratch.  The arrays stay with the context and are reused by later calls of any size. */
+int wf_order_records(wf_ctx* ctx, const wf_order_in* in, wf_order_out* out);
 
 /* ---- --write-details (orgscorer.py:766-812, 931-937) --------------------------------
  * With details on, the next wf_score (staged mode) also records, for every roll-up level,

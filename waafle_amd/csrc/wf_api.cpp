@@ -58,6 +58,7 @@ struct wf_ctx {
   int wave_two = 2;                // wf_set_option(WF_OPT_WAVE_TWO)
   wf::StagedState* staged = nullptr;
   wf::MapState* map = nullptr;     // paired-read mapper: its index and staging (wf_map_index)
+  wf::OrderState* order = nullptr; // wf_order_records: its device arrays
   // --write-details
   bool details_on = false;
   wf::DetailsSink det;
@@ -238,6 +239,7 @@ void wf_free(wf_ctx* ctx) {
   for (DevBuf* b : bufs) release(*b);
   if (ctx->staged) wf::staged_destroy(ctx->staged);
   if (ctx->map) wf::map_destroy(ctx->map);
+  if (ctx->order) wf::order_destroy(ctx->order);
   for (hipEvent_t ev : ctx->ev_pool) (void)hipEventDestroy(ev);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
   delete ctx;
@@ -686,6 +688,70 @@ int wf_hits_from_records(wf_ctx* ctx, const wf_hit_records* rc, const wf_hit_tab
       (rv = download(ctx, o->hit_key, a.hit_key, n)))
     return rv;
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return WF_OK;
+}
+
+// The checks of wf_order_records and, in the same pass, the plan of the sort key: each field's
+// least value and the bits its range needs in this call.
+static int check_order_records(wf_ctx* ctx, const wf_order_in* in, const wf_order_out* o, wf::OrderPlan* plan) {
+  if (!in || !o) return fail(ctx, WF_E_BADINPUT, "null records/out");
+  const int64_t n = in->n;
+  if (n < 0 || n >= (int64_t)1 << 31) return fail(ctx, WF_E_BADINPUT, "n outside [0, 2^31)");
+  if (in->max_target_seqs < 1) return fail(ctx, WF_E_BADINPUT, "max_target_seqs %lld", (long long)in->max_target_seqs);
+  const int given = (in->qspan != nullptr) + (in->sspan != nullptr) + (in->gaps != nullptr);
+  if (given != 0 && given != 3) return fail(ctx, WF_E_BADINPUT, "only some of qspan, sspan, gaps given");
+  if (n == 0) return WF_OK;
+  if (!in->contig || !in->subject || !in->minus || !in->qstart || !in->sstart || !in->length || !in->matches)
+    return fail(ctx, WF_E_BADINPUT, "null record arrays");
+  if (!o->order) return fail(ctx, WF_E_BADINPUT, "null order");
+  const bool gapped = given == 3;
+  int64_t lo[wf::kOrderFields], hi[wf::kOrderFields];
+  for (int64_t i = 0; i < n; ++i) {
+    const long long r = (long long)i;
+    if (in->contig[i] < 0) return fail(ctx, WF_E_BADINPUT, "record %lld: contig %d", r, in->contig[i]);
+    if (in->subject[i] < 0) return fail(ctx, WF_E_BADINPUT, "record %lld: subject %d", r, in->subject[i]);
+    if (in->minus[i] > 1) return fail(ctx, WF_E_BADINPUT, "record %lld: minus is %d", r, (int)in->minus[i]);
+    const int64_t m = in->matches[i], len = in->length[i];
+    const int64_t v[wf::kOrderFields] = {in->contig[i], gapped ? 6 * m - 4 * len - in->gaps[i] : 3 * m - 2 * len,
+                                         in->subject[i], in->minus[i], in->qstart[i], in->sstart[i],
+                                         gapped ? in->qspan[i] : 0, gapped ? in->sspan[i] : 0};
+    for (int f = 0; f < wf::kOrderFields; ++f) {
+      if (i == 0 || v[f] < lo[f]) lo[f] = v[f];
+      if (i == 0 || v[f] > hi[f]) hi[f] = v[f];
+    }
+  }
+  for (int f = 0; f < wf::kOrderFields; ++f) {
+    uint64_t range = (uint64_t)(hi[f] - lo[f]);              // below 2^37: int32 columns, |score| < 2^36
+    plan->bits[f] = 0;
+    for (; range; range >>= 1) ++plan->bits[f];
+    plan->base[f] = f == 1 ? hi[f] : lo[f];                  // the score's field holds greatest - score
+  }
+  // no contig holds more subjects than the call has subject values or records
+  plan->limit = in->max_target_seqs;
+  plan->rank = plan->limit < std::min<int64_t>(n, hi[2] - lo[2] + 1);
+  return WF_OK;
+}
+
+int wf_order_records(wf_ctx* ctx, const wf_order_in* in, wf_order_out* o) {
+  if (!ctx) return WF_E_BADINPUT;
+  wf::OrderPlan plan{};
+  int rv = check_order_records(ctx, in, o, &plan);
+  if (rv) return rv;
+  if (in->n == 0) {
+    o->n_kept = 0;
+    return WF_OK;
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (!ctx->order) ctx->order = wf::order_create();
+  const wf::OrderIn oin{in->n, in->contig, in->subject, in->minus, in->qstart, in->sstart, in->length, in->matches,
+                        in->qspan, in->sspan, in->gaps};
+  int64_t n_kept = 0;
+  const wf::OrderOut out{&n_kept, o->order, o->contig, o->subject, o->minus, o->qstart, o->qspan, o->sstart, o->sspan,
+                         o->length, o->matches};
+  std::string err;
+  const int rc = wf::order_run(ctx->order, oin, plan, out, ctx->stream, &err);
+  if (rc) return fail(ctx, rc, "%s", err.c_str());
+  o->n_kept = n_kept;
   return WF_OK;
 }
 

@@ -257,6 +257,33 @@ struct HitsArgs {
 };
 hipError_t launch_hits(const HitsArgs& a, hipStream_t s);
 
+// the table's order and --max-target-seqs (wf_order.hip).  Host pointers; the
+// caller (wf_order_records) has checked the records and made the plan in one pass over them.
+// The key's fields, most significant first: contig, greatest score - score, subject, minus,
+// qstart, sstart, qspan, sspan; field f holds value - base[f] (the score: base[1] - score) in
+// bits[f] bits, which must hold every record's value (0 bits: all records agree, or ungapped
+// records' spans).  rank: some contig may hold more than `limit` subjects, so the pairs are ranked.
+// 0, -2 (HIP), or -4 when device memory cannot be had, with nothing written; returns after the
+// device is done.
+constexpr int kOrderFields = 8;
+struct OrderState;
+OrderState* order_create();
+void order_destroy(OrderState* st);
+struct OrderIn {
+  int64_t n;                               // 0 < n < 2^31
+  const int32_t* contig; const int32_t* subject; const uint8_t* minus; const int32_t* qstart; const int32_t* sstart;
+  const int32_t* length; const int32_t* matches;
+  const int32_t* qspan; const int32_t* sspan; const int32_t* gaps;    // all null: ungapped
+};
+struct OrderPlan { int64_t base[kOrderFields]; int bits[kOrderFields]; int rank; int64_t limit; };
+struct OrderOut {                          // the columns: null, or room for n
+  int64_t* n_kept; int64_t* order;
+  int32_t* contig; int32_t* subject; uint8_t* minus; int32_t* qstart; int32_t* qspan; int32_t* sstart; int32_t* sspan;
+  int32_t* length; int32_t* matches;
+};
+int order_run(OrderState* st, const OrderIn& in, const OrderPlan& plan, const OrderOut& out, hipStream_t s,
+              std::string* err);
+
 // --write-details: per roll-up level, the evaluated (active) contigs and the segment
 // records of the level, copied to the host (wf_staged.hip details_level)
 struct DetailsLevel {

@@ -183,6 +183,17 @@ class WfHitsOut(C.Structure):
                 ("hit_sysmask", _P), ("hit_key", _P)]
 
 
+class WfOrderIn(C.Structure):
+    _fields_ = [("n", C.c_int64), ("max_target_seqs", C.c_int64), ("contig", _P), ("subject", _P), ("minus", _P),
+                ("qstart", _P), ("sstart", _P), ("length", _P), ("matches", _P), ("qspan", _P), ("sspan", _P),
+                ("gaps", _P)]
+
+
+class WfOrderOut(C.Structure):
+    _fields_ = [("n_kept", C.c_int64), ("order", _P), ("contig", _P), ("subject", _P), ("minus", _P),
+                ("qstart", _P), ("qspan", _P), ("sstart", _P), ("sspan", _P), ("length", _P), ("matches", _P)]
+
+
 class WfDetails(C.Structure):
     _fields_ = [("n_evals", C.c_int64), ("eval_contig", _P), ("eval_level", _P),
                 ("n_segs", C.c_int64), ("seg_level", _P), ("seg_contig", _P), ("seg_clade", _P),
@@ -231,6 +242,7 @@ SIGNATURES = {
     "wf_search_mask": (C.c_int, [C.c_void_p, C.POINTER(WfDustParams), C.POINTER(WfDustResult)]),
     "wf_hits_from_records": (C.c_int, [C.c_void_p, C.POINTER(WfHitRecords), C.POINTER(WfHitTables),
                                        C.POINTER(WfHitsOut)]),
+    "wf_order_records": (C.c_int, [C.c_void_p, C.POINTER(WfOrderIn), C.POINTER(WfOrderOut)]),
     "wf_details_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "wf_details_read": (C.c_int, [C.c_void_p, C.POINTER(WfDetails)]),
 }

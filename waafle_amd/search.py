@@ -28,7 +28,8 @@ eighths of the bytes go to the device.  The table is the same either way.
 
 Host side (this module): the streaming subject-FASTA reader, the reader of a packed database,
 the calls into wf_search / wf_search_gapped and their packed forms, the ordering and
---max-target-seqs step and the row writer.
+--max-target-seqs step (order_records; with `--order-on device` wf_order_records computes the
+same on the GPU) and the row writer.
 """
 from __future__ import annotations
 
@@ -514,6 +515,58 @@ def order_records(rec, max_target_seqs=MAX_TARGET_SEQS):
     return idx[o2]
 
 
+ORDER_COLUMNS = (("contig", np.int32), ("subject", np.int32), ("minus", np.uint8), ("qstart", np.int32),
+                 ("qspan", np.int32), ("sstart", np.int32), ("sspan", np.int32), ("length", np.int32),
+                 ("matches", np.int32))                      # hits.RECORD_COLUMNS: those of wf_hit_records
+
+
+def order_records_device(ctx, rec, max_target_seqs=MAX_TARGET_SEQS, gather=False, out=None):
+    """order_records on the GPU (wf_order_records): the same indices.  `ctx`: an
+    open Searcher, mapper.Mapper or engine.GpuScorer (anything with the library and a context
+    handle).  gather: returns (order, columns), the columns what hits.record_columns(rec,
+    order) gives.  out: {"order": int64 [n], column: [n] ...} to write into (a refused call
+    leaves them as they are).  Raises lib.WaafleHipError; its code is lib.WF_E_NOMEM when the
+    device has no room for the call (order_with falls back to the host then)."""
+    so, h = getattr(ctx, "so", None) or ctx.lib, ctx.h
+    gapped = "gaps" in rec
+    fields = GAP_RECORD_FIELDS if gapped else RECORD_FIELDS
+    held = {f: np.ascontiguousarray(rec[f], dtype=dt) for f, dt in fields}
+    n = len(held["contig"])
+    out = {} if out is None else out
+    if "order" not in out:
+        out["order"] = np.zeros(n, np.int64)
+    if gather:
+        for f, dt in ORDER_COLUMNS:
+            out.setdefault(f, np.zeros(n, dt))
+    a = L.WfOrderIn(n=n, max_target_seqs=int(max_target_seqs),
+                    **{f: L.ptr(held[f]) if f in held else None for f, _ in GAP_RECORD_FIELDS})
+    o = L.WfOrderOut(n_kept=-1, **{f: L.ptr(out[f]) for f in out})
+    rc = so.wf_order_records(h, C.byref(a), C.byref(o))
+    if rc != L.WF_OK:
+        raise L.WaafleHipError(rc, so.wf_last_error(h).decode())
+    k = int(o.n_kept)
+    order = out["order"][:k]
+    return (order, {f: out[f][:k] for f, _ in ORDER_COLUMNS}) if gather else order
+
+
+def order_with(ctx, rec, max_target_seqs, order_on="host", gather=False, say=lambda *a: None):
+    """The order of `rec` by the host function or, with order_on "device", on the GPU of the open
+    context `ctx`; when the device has no room, one line through `say` and the host function.
+    gather: (order, the nine columns of hits.record_columns)."""
+    if order_on == "device":
+        try:
+            return order_records_device(ctx, rec, max_target_seqs, gather=gather)
+        except L.WaafleHipError as exc:
+            if exc.code != L.WF_E_NOMEM:
+                raise
+            say("  no device memory to order {:,} records: ordering on the host".format(len(rec["contig"])))
+    order = order_records(rec, max_target_seqs)
+    if not gather:
+        return order
+    from . import hits
+    return order, hits.record_columns(rec, order)
+
+
 def bitscore_text(score):
     bits = (LAMBDA * score - math.log(K)) / math.log(2)
     return str(int(bits)) if bits > 99.9 else "%.1f" % bits
@@ -560,17 +613,18 @@ def format_rows(rec, order, contig_names, contig_lens, subject_ids, subject_lens
 
 def search_files(query, db, out_path, device=0, chunk_bases=CHUNK_BASES, max_target_seqs=MAX_TARGET_SEQS,
                  say=lambda *a: None, gapped=False, band=15, xdrop_gap=30, dust=False, dust_window=64,
-                 dust_level=20, dust_out=None, **params):
+                 dust_level=20, dust_out=None, order_on="host", **params):
     """The native search of `db`, a genes' FASTA or a packed database (makedb: told by its
     magic), against the contigs `query`, written to `out_path`;
     gapped: the alignments of the gapped extension in place of the ungapped HSPs; dust: seeds
-    from the contigs' unmasked S-mers only, and with dust_out the masked intervals written there.
+    from the contigs' unmasked S-mers only, and with dust_out the masked intervals written there;
+    order_on "device": the table's order from wf_order_records in place of order_records.
     Returns the searcher's counters plus rows, subjects and database bases."""
     names, seq, off = mapper.read_fasta(query)
-    rec, ids, lens, stats = search_records(names, seq, off, db, device=device, chunk_bases=chunk_bases, say=say,
-                                           gapped=gapped, band=band, xdrop_gap=xdrop_gap, dust=dust,
-                                           dust_window=dust_window, dust_level=dust_level, dust_out=dust_out, **params)
-    order = order_records(rec, max_target_seqs)
+    rec, ids, lens, stats, order = search_ordered(
+        names, seq, off, db, max_target_seqs, order_on=order_on, device=device, chunk_bases=chunk_bases, say=say,
+        gapped=gapped, band=band, xdrop_gap=xdrop_gap, dust=dust, dust_window=dust_window, dust_level=dust_level,
+        dust_out=dust_out, **params)
     rows = format_rows(rec, order, names, np.diff(off), ids, lens, int(lens.sum()))
     with open(out_path, "w") as fh:
         fh.write("".join(r + "\n" for r in rows))
@@ -584,30 +638,49 @@ def search_records(names, seq, off, db, device=0, chunk_bases=CHUNK_BASES, say=l
     (names, seq, off as mapper.read_fasta gives them).  Returns (records with database-wide
     subject numbers, in the order found; the subjects' ids; their lengths; the searcher's
     counters)."""
-    fields = GAP_RECORD_FIELDS if gapped else RECORD_FIELDS
-    ids, lens, parts = [], [], []
     with Searcher(seq, off, device=device, band=band, xdrop_gap=xdrop_gap, dust=dust, dust_window=dust_window,
                   dust_level=dust_level, **params) as s:
-        if dust:
-            say("  {:,} of {:,} contig bases masked; {:,} of {:,} seeds kept".format(
-                s.dust_stats["masked_bases"], len(seq), s.dust_stats["kmers_after"], s.dust_stats["kmers_before"]))
-            if dust_out:
-                with open(dust_out, "w") as fh:
-                    fh.write("".join(r + "\n" for r in format_mask_rows(mask_intervals(s.mask(), off), names)))
-        pdb = PackedDb(db) if is_packed_db(db) else None
-        for item in (pdb.chunks(chunk_bases) if pdb else iter_subject_chunks(db, chunk_bases)):
-            if pdb:
-                cid, coff = range(item.first, item.last), item.off
-                rec = search_chunk(s, item, None, gapped)
-            else:
-                cid, cseq, coff = item
-                rec = search_chunk(s, cseq, coff, gapped)
-            rec["subject"] = rec["subject"] + np.int32(len(ids))
-            parts.append(rec)
-            ids += cid                                       # a packed database: its subjects' numbers
-            lens.append(np.diff(coff))
-            say("  {:,} subjects searched, {:,} records".format(len(ids), sum(len(p["contig"]) for p in parts)))
-        stats = dict(s.stats)
+        return _records_of(s, names, seq, off, db, chunk_bases, say, gapped, dust, dust_out)
+
+
+def search_ordered(names, seq, off, db, max_target_seqs=MAX_TARGET_SEQS, order_on="host", gather=False,
+                   device=0, chunk_bases=CHUNK_BASES, say=lambda *a: None, gapped=False, band=15, xdrop_gap=30,
+                   dust=False, dust_window=64, dust_level=20, dust_out=None, before_order=None, **params):
+    """search_records and the table's order of its records (order_with), found while the
+    searcher's context is still open: what search_records returns, then the order, or with
+    gather (order, columns).  before_order: called between the two (a timer's lap)."""
+    with Searcher(seq, off, device=device, band=band, xdrop_gap=xdrop_gap, dust=dust, dust_window=dust_window,
+                  dust_level=dust_level, **params) as s:
+        found = _records_of(s, names, seq, off, db, chunk_bases, say, gapped, dust, dust_out)
+        if before_order:
+            before_order()
+        return found + (order_with(s, found[0], max_target_seqs, order_on, gather=gather, say=say),)
+
+
+def _records_of(s, names, seq, off, db, chunk_bases, say, gapped, dust, dust_out):
+    """search_records on the open Searcher `s`"""
+    fields = GAP_RECORD_FIELDS if gapped else RECORD_FIELDS
+    ids, lens, parts = [], [], []
+    if dust:
+        say("  {:,} of {:,} contig bases masked; {:,} of {:,} seeds kept".format(
+            s.dust_stats["masked_bases"], len(seq), s.dust_stats["kmers_after"], s.dust_stats["kmers_before"]))
+        if dust_out:
+            with open(dust_out, "w") as fh:
+                fh.write("".join(r + "\n" for r in format_mask_rows(mask_intervals(s.mask(), off), names)))
+    pdb = PackedDb(db) if is_packed_db(db) else None
+    for item in (pdb.chunks(chunk_bases) if pdb else iter_subject_chunks(db, chunk_bases)):
+        if pdb:
+            cid, coff = range(item.first, item.last), item.off
+            rec = search_chunk(s, item, None, gapped)
+        else:
+            cid, cseq, coff = item
+            rec = search_chunk(s, cseq, coff, gapped)
+        rec["subject"] = rec["subject"] + np.int32(len(ids))
+        parts.append(rec)
+        ids += cid                                       # a packed database: its subjects' numbers
+        lens.append(np.diff(coff))
+        say("  {:,} subjects searched, {:,} records".format(len(ids), sum(len(p["contig"]) for p in parts)))
+    stats = dict(s.stats)
     rec = {f: np.concatenate([p[f] for p in parts]) if parts else np.zeros(0, dt) for f, dt in fields}
     lens = np.concatenate(lens) if lens else np.zeros(0, np.int64)
     return rec, (pdb.ids if pdb else ids), lens, stats
@@ -649,6 +722,9 @@ def build_parser():
     g.add_argument("--min-score", type=int, default=DEFAULTS["min_score"], metavar="<int>",
                    help="least raw score (match +1, mismatch -2) reported")
     g.add_argument("--max-target-seqs", type=int, default=MAX_TARGET_SEQS, metavar="<int>")
+    g.add_argument("--order-on", choices=["host", "device"], default="host",
+                   help="where the table's order and --max-target-seqs are computed: host (numpy) or\n"
+                        "device (wf_order_records on the GPU; the same table)\n[default: host]")
     g.add_argument("--chunk-bases", type=int, default=CHUNK_BASES, metavar="<int>",
                    help="subject bases per device call")
     g.add_argument("--gpu", type=int, default=0, metavar="<int>")
@@ -711,7 +787,8 @@ def main(argv=None):
                              seed_length=args.seed_length, seed_stride=args.seed_stride,
                              max_seed_hits=args.max_seed_hits, xdrop=args.xdrop, min_score=args.min_score,
                              gapped=args.gapped, band=args.band, xdrop_gap=args.xdrop_gap, dust=args.dust,
-                             dust_window=args.dust_window, dust_level=args.dust_level, dust_out=args.dust_out)
+                             dust_window=args.dust_window, dust_level=args.dust_level, dust_out=args.dust_out,
+                             order_on=args.order_on)
     except (inputs.InputError, OSError, L.WaafleHipError) as exc:
         die(str(exc))
     inputs.say("Finished successfully ({:,} rows from {:,} subjects; {:,} seed hits).".format(

@@ -8,7 +8,9 @@ through `wf_hits_from_records` to the hit arrays on the device,
 and `wf_score` read those.  The three TSVs are byte for byte those of the three commands run one
 after another with the same flags.  `--gff` takes user-supplied gene calls in place of the gene
 caller; `--write-blastout` and `--write-gff` also write the files the first two commands would,
-through their writers (for inspection: they cost what those writers cost).
+through their writers (for inspection: they cost what those writers cost).  `--order-on device`
+puts the records in the table's order, applies `--max-target-seqs` and gathers their columns on
+the GPU as well (`wf_order_records`); the files are the same.
 
 One GPU (`--gpu`); no `--write-details`, no blastn searcher.  A contig name that occurs twice in
 the FASTA is an error here, as for the native search.
@@ -75,14 +77,21 @@ def run(args, say):
     names, seq, off = mapper.read_fasta(args.contigs)
     qlen = np.diff(off)
     gapped = bool(args.gapped)
-    rec, ids, lens, stats = search.search_records(
-        names, seq, off, args.db, device=args.gpu, chunk_bases=args.chunk_bases, say=say, gapped=gapped,
+    found = dict(
+        device=args.gpu, chunk_bases=args.chunk_bases, say=say, gapped=gapped,
         band=args.band, xdrop_gap=args.xdrop_gap, dust=args.dust, dust_window=args.dust_window,
         dust_level=args.dust_level, dust_out=args.dust_out, seed_length=args.seed_length,
         seed_stride=args.seed_stride, max_seed_hits=args.max_seed_hits, xdrop=args.xdrop, min_score=args.min_score)
-    lap("search")
-    order = search.order_records(rec, args.max_target_seqs)
-    cols = hits.record_columns(rec, order)
+    if args.order_on == "device":
+        # wf_order_records with gathering, on the searcher's context before it closes
+        rec, ids, lens, stats, (order, cols) = search.search_ordered(
+            names, seq, off, args.db, args.max_target_seqs, order_on="device", gather=True,
+            before_order=lambda: lap("search"), **found)
+    else:
+        rec, ids, lens, stats = search.search_records(names, seq, off, args.db, **found)
+        lap("search")
+        order = search.order_records(rec, args.max_target_seqs)
+        cols = hits.record_columns(rec, order)
     lap("order")
     if args.write_blastout:
         rows = search.format_rows(rec, order, names, qlen, ids, lens, int(lens.sum()))
