@@ -35,7 +35,9 @@ extern "C" {
                                     still 6 (additive): wf_search_packed, wf_search_gapped_packed,
                                                         wf_search_chunk_planes;
                                     still 6 (additive): wf_hits_from_records;
-                                    still 6 (additive): wf_order_records */
+                                    still 6 (additive): wf_order_records;
+                                    still 6 (additive): WF_OPT_SEARCH_REPORT, wf_search_report,
+                                                        wf_search_report_gapped */
 
 enum wf_status {
   WF_OK = 0,
@@ -93,9 +95,13 @@ enum wf_mode { WF_MODE_STAGED = 0, WF_MODE_LEVEL0 = 2, WF_MODE_WAVES = 3 };
  *   the contigs explain_one settles from the clades present on every locus (one-run gene
  *   scores), without the wave form's sort and segment table; the wave form runs the rest.
  *   0: the wave form runs every contig (a test setting: it exercises that path on every
- *   input). */
+ *   input).
+ * WF_OPT_SEARCH_REPORT: where the reporting step of the four search calls and of
+ *   wf_search_report / wf_search_report_gapped runs: 0 (default) on the host,
+ *   1 on the device; the same records, counters and statuses either way.
+ */
 enum wf_option { WF_OPT_SPARSE_BIG = 1, WF_OPT_ATT_LIMIT = 2, WF_OPT_WAVE_TWO = 3, WF_OPT_DUMP_CAP = 4,
-                 WF_OPT_TRIAGE = 5 };
+                 WF_OPT_TRIAGE = 5, WF_OPT_SEARCH_REPORT = 6 };
 
 typedef struct wf_ctx wf_ctx;
 
@@ -521,6 +527,52 @@ int wf_search_gapped_packed(wf_ctx* ctx, const wf_search_packed_subjects* subjec
    no seed slot (no subject as long as a seed, no index entries) leaves none.  WF_E_STATE when no
    chunk is resident; WF_E_BADINPUT for another strand, null arrays or another `words`. */
 int wf_search_chunk_planes(wf_ctx* ctx, int strand, uint32_t* lo, uint32_t* hi, uint32_t* nn, int64_t words);
+
+/* The reporting step on its own (DESIGN.md §12.1 "Reporting", §12.5 "Reporting", §12.8), in the
+ * form WF_OPT_SEARCH_REPORT selects; no index is needed.  wf_search_report: raw HSPs, [b, e) on the
+ * variant at diagonal delta (contig position - variant position) with score = matches - 2
+ * mismatches, to the records wf_search gives for them; out->raw_hsps = n, the other counters 0.
+ * wf_search_report_gapped: anchors (i0 on the variant, j0 contig-local) with the two sides of
+ * their gapped extension (H in half units, p variant bases, q contig bases, g gap columns) to
+ * the records wf_search_gapped gives; out->anchors = n and out->raw_alignments are set. */
+typedef struct wf_report_hsps {   /* host memory, [n] each */
+  int64_t n;                      /* < 2^31 */
+  int32_t min_score;              /* >= 1 */
+  int32_t _pad;
+  const int32_t* contig;          /* >= 0 */
+  const int32_t* subject;         /* >= 0, < 2^30 */
+  const uint8_t* minus;           /* 0 / 1 */
+  const int32_t* delta;
+  const int32_t* b;               /* >= 0 */
+  const int32_t* e;               /* > b */
+  const int32_t* score;           /* score + 2 (e - b) = 3 matches, 0 <= matches <= e - b */
+} wf_report_hsps;
+
+typedef struct wf_report_anchors { /* host memory, [n] each */
+  int64_t n;                      /* < 2^31 */
+  int32_t min_score;              /* >= 1 */
+  int32_t _pad;
+  const int32_t* contig;
+  const int32_t* subject;
+  const uint8_t* minus;
+  const int32_t* i0;
+  const int32_t* j0;
+  const int32_t* left_H;  const int32_t* left_p;  const int32_t* left_q;  const int32_t* left_g;
+  const int32_t* right_H; const int32_t* right_p; const int32_t* right_q; const int32_t* right_g;
+} wf_report_anchors;
+
+/* Both: the capacity / n / WF_E_NOMEM-and-repeat protocol and the order of the search calls.
+   n = 0 is valid.  WF_E_BADINPUT, checked on the host before anything is uploaded, so nothing is
+   written: a null struct, a null column with n > 0 or a null result array with capacity > 0, n
+   outside [0, 2^31), a negative capacity, min_score < 1; and, named by its first record in
+   wf_last_error: contig or subject < 0 (subject >= 2^30), minus above 1; ungapped: b < 0, e <= b,
+   score + 2 (e - b) no multiple of 3 or outside 0 .. 3 (e - b), b + delta outside int32; gapped: a negative p, q or g,
+   sspan + qspan - gaps odd, (score2 + 5 gaps + 4 pairs) / 6 inexact or outside 0 .. length, a field of
+   the alignment outside int32.  Two HSPs equal in (subject, minus, contig, delta, b, e) cover the same
+   bases and must have the same score: which score survives is otherwise undefined.
+   Returns after the work is done. */
+int wf_search_report(wf_ctx* ctx, const wf_report_hsps* hsps, wf_search_result* out);
+int wf_search_report_gapped(wf_ctx* ctx, const wf_report_anchors* anchors, wf_search_gap_result* out);
 
 /* Low-complexity masking.  wf_search_mask computes the symmetric-DUST mask
  * (Morgulis et al. 2006, the published definition) of the contigs the context holds and

@@ -4,7 +4,8 @@ one MI355X.
     python scripts/search_bench.py [--contigs 10000 --contig-length 5000 --db-bases 200000000
                                     --subject-length 1000 --homolog-share 0.01 --chunk-bases 67108864
                                     --indel-rate 0.003 --gapped --band 15 --xdrop-gap 30
-                                    --low-complexity 2000 --dust --packed]
+                                    --low-complexity 2000 --dust --packed --report-on device
+                                    --family 1000 --compare-report 3]
     python scripts/search_bench.py --files [--tmp-dir DIR]
 
 Not bench.py (the flagship workload); the numbers go to DESIGN.md §12 and profiles/search/.
@@ -18,7 +19,14 @@ is cut longer and trimmed).  --gapped runs `Searcher.search_gapped` in place of
 masks the contigs (`wf_search_mask`) before the search and reports the mask's
 counters and the wall of that call (mask kernel, index rebuild and the mask's copy to the
 host).  The search parameters are the defaults (S 21, T 8, max_occ 64, X 20,
-min_score 28).  The GPU step runs in a child process under its own time limit
+min_score 28).  --family n plants every gene n times: n database subjects cut from the same
+place of the same contig, each with its own 0..2 % substitutions (a gene family present in n
+species), so that one chunk carries 10^5 to 10^7 raw HSPs of which the reporting step keeps few.
+--report-on device runs that step on the GPU (WF_OPT_SEARCH_REPORT).
+--compare-report k measures both forms in one process: two searchers on the same contigs, one
+warm-up pass over every chunk each, then k passes each, interleaved host, device, host, ...; a
+pass's wall is the sum of its search calls, which return after a synchronisation; the records of
+the two forms must be equal.  The GPU step runs in a child process under its own time limit
 (--step-timeout); when it fails or runs out of time nothing more is started.
 
   search  `Searcher.search` on host-resident subjects in chunks of --chunk-bases (copies in
@@ -72,6 +80,12 @@ def parse(argv=None):
     ap.add_argument("--low-complexity", type=int, default=0,
                     help="low-complexity stretches written over the contigs, and as many over random subjects")
     ap.add_argument("--dust", action="store_true", help="wf_search_mask on the contigs before the search")
+    ap.add_argument("--report-on", choices=["host", "device"], default="host",
+                    help="where each chunk's reporting step runs")
+    ap.add_argument("--family", type=int, default=0, metavar="<copies>",
+                    help="every planted gene in this many near-identical subjects (0: each planted once)")
+    ap.add_argument("--compare-report", type=int, default=0, metavar="<runs>",
+                    help="both forms of the reporting step in one process, interleaved, this many passes each")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--gpu", type=int, default=0)
     ap.add_argument("--packed", action="store_true", help="the subjects as bit planes (wf_search_packed)")
@@ -93,8 +107,11 @@ def make_workload(a):
     hom = np.flatnonzero(rng.random(n) < a.homolog_share)
     c = rng.integers(0, a.contigs, len(hom))
     p = rng.integers(0, a.contig_length - L + 1, len(hom))
+    if a.family > 0:                                          # the members of a family share their gene's place
+        first = np.arange(len(hom)) // a.family * a.family
+        c, p = c[first], p[first]
     cut = codes[(off[c] + p)[:, None] + np.arange(L, dtype=np.int64)[None, :]]
-    rate = rng.random(len(hom))[:, None] * 0.10               # 90..100 % identity
+    rate = rng.random(len(hom))[:, None] * (0.02 if a.family > 0 else 0.10)   # 90..100 % identity; a family 98..100 %
     sub = rng.random(cut.shape) < rate
     cut = (cut + sub * rng.integers(1, 4, cut.shape, dtype=np.uint8)).astype(np.uint8) & 3
     if a.indel_rate > 0:                                      # a stream of its own: rate 0 is the old workload
@@ -154,7 +171,9 @@ def step_search(a):
     walls, records, found, span = [], 0, np.zeros(n, bool), np.zeros(n, np.int64)
     gap = dict(band=a.band, xdrop_gap=a.xdrop_gap) if a.gapped else {}
     dust = {}
-    with search.Searcher(ASCII[codes], off, device=a.gpu, **gap) as s:
+    if a.compare_report > 0:
+        return compare_report(a, search, codes, off, subj, per, db, gap)
+    with search.Searcher(ASCII[codes], off, device=a.gpu, report_on=a.report_on, **gap) as s:
         if a.dust:
             t0 = time.perf_counter()
             s.apply_mask(len(codes))
@@ -171,7 +190,7 @@ def step_search(a):
         else:
             run(ASCII[subj[:w]].reshape(-1), np.arange(w + 1, dtype=np.int64) * L)
         s.stats = dict.fromkeys(s.stats, 0)
-        copied = []
+        copied, raw_per_chunk, records_per_chunk = [], [], []
         for lo in range(0, n, per):
             hi = min(lo + per, n)
             if a.packed:
@@ -189,18 +208,80 @@ def step_search(a):
             records += len(rec["contig"])
             found[rec["subject"].astype(np.int64) + lo] = True
             np.maximum.at(span, rec["subject"].astype(np.int64) + lo, rec["sspan" if a.gapped else "length"])
+            raw_per_chunk.append(s.stats["raw_hsps"] - sum(raw_per_chunk))
+            records_per_chunk.append(len(rec["contig"]))
         stats = dict(s.stats)
     total = sum(walls)
     return dict(search_s=total, chunk_s=walls, chunk_bases=per * L, subject_bases_per_s=n * L / total,
                 subjects=n, homologs=int(len(hom)), homologs_found_fraction=float(found[hom].mean()) if len(hom) else 0.0,
                 homologs_scov_075=int((span[hom] >= 0.75 * L).sum()), gapped=bool(a.gapped),
-                packed=bool(a.packed), h2d_bytes_per_chunk=copied,
+                packed=bool(a.packed), h2d_bytes_per_chunk=copied, report_on=a.report_on, family=a.family,
+                raw_hsps_per_chunk=raw_per_chunk, records_per_chunk=records_per_chunk,
                 anchors=stats.get("anchors", 0), raw_alignments=stats.get("raw_alignments", 0),
                 other_subjects_with_records=int(found.sum() - found[hom].sum()), records=records,
                 seed_hits=stats["seed_hits"], seeds_skipped=stats["seeds_skipped"], raw_hsps=stats["raw_hsps"],
                 skipped_share=stats["seeds_skipped"] / max(stats["seed_hits"], 1), dust=dust,
                 timing="host-resident subjects: copies in and out and the host's de-duplication included, "
                        "one warm-up chunk")
+
+
+def compare_report(a, search, codes, off, subj, per, db, gap):
+    """--compare-report: the two forms of the reporting step on the same chunks in one process"""
+    n, L = subj.shape
+    chunks = []
+    for lo in range(0, n, per):
+        hi = min(lo + per, n)
+        chunks.append(search.PackedChunk(db, lo, hi) if a.packed else
+                      (ASCII[subj[lo:hi]].reshape(-1), np.arange(hi - lo + 1, dtype=np.int64) * L))
+    forms = ("host", "device")
+    fields = [f for f, _ in (search.GAP_RECORD_FIELDS if a.gapped else search.RECORD_FIELDS)]
+    searchers = {w: search.Searcher(ASCII[codes], off, device=a.gpu, report_on=w, dust=a.dust, **gap) for w in forms}
+    walls = {w: [] for w in forms}
+    chunk_walls = {w: [] for w in forms}
+    out = {}
+    try:
+        def one_pass(w, keep):
+            s = searchers[w]
+            s.stats = dict.fromkeys(s.stats, 0)
+            t, recs, raw, per_chunk = [], [], [], []
+            for ch in chunks:
+                before = s.stats["raw_hsps"]
+                t0 = time.perf_counter()
+                if a.packed:
+                    rec = s.search_gapped_packed(ch) if a.gapped else s.search_packed(ch)
+                else:
+                    rec = s.search_gapped(*ch) if a.gapped else s.search(*ch)
+                t.append(time.perf_counter() - t0)
+                raw.append(s.stats["raw_hsps"] - before)
+                per_chunk.append(len(rec["contig"]))
+                if keep:
+                    recs.append(rec)
+            return t, recs, raw, per_chunk, dict(s.stats)
+
+        kept = {}
+        for w in forms:                                       # the warm-up pass; its records are compared
+            _, kept[w], raw, per_chunk, stats = one_pass(w, True)
+            out[w] = dict(raw_hsps_per_chunk=raw, records_per_chunk=per_chunk, stats=stats)
+        equal = all((x[f] == y[f]).all() if len(x[f]) == len(y[f]) else False
+                    for x, y in zip(kept["host"], kept["device"]) for f in fields)
+        equal = equal and out["host"]["stats"] == out["device"]["stats"]
+        kept.clear()
+        for _ in range(a.compare_report):
+            for w in forms:
+                t = one_pass(w, False)[0]
+                walls[w].append(sum(t))
+                chunk_walls[w].append(t)
+    finally:
+        for s in searchers.values():
+            s.close()
+    return dict(compare_report=a.compare_report, gapped=bool(a.gapped), packed=bool(a.packed), family=a.family,
+                chunks=len(chunks), chunk_bases=per * L, subjects=n, records_and_counters_equal=bool(equal),
+                raw_hsps_per_chunk=out["host"]["raw_hsps_per_chunk"], records_per_chunk=out["host"]["records_per_chunk"],
+                anchors=out["host"]["stats"].get("anchors", 0), seed_hits=out["host"]["stats"]["seed_hits"],
+                pass_s=walls, chunk_s=chunk_walls,
+                timing="each form: one warm-up pass over every chunk, then the passes of the two forms interleaved; "
+                       "a pass is the sum of its search calls, host-resident subjects, each returning after a "
+                       "synchronisation")
 
 
 def evict(path):
@@ -270,7 +351,8 @@ def main(argv=None):
                              subject_length=a.subject_length, homolog_share=a.homolog_share,
                              identity="90..100 %", indel_rate=a.indel_rate, seed=a.seed, gapped=a.gapped,
                              band=a.band, xdrop_gap=a.xdrop_gap, low_complexity=a.low_complexity, dust=a.dust,
-                             packed=a.packed, files=a.files,
+                             packed=a.packed, files=a.files, report_on=a.report_on, family=a.family,
+                             compare_report=a.compare_report,
                              params=dict(seed_length=21, seed_stride=8, max_seed_hits=64, xdrop=20, min_score=28)))
     passed = [x for x in (argv if argv is not None else sys.argv[1:])]
     cmd = [sys.executable, os.path.abspath(__file__), "--step", "files" if a.files else "search"] + passed

@@ -16,11 +16,12 @@ SOURCES = [os.path.join(CSRC, "wf_staged.hip"), os.path.join(CSRC, "wf_fast.hip"
            os.path.join(CSRC, "wf_junctions.hip"), os.path.join(CSRC, "wf_map.hip"),
            os.path.join(CSRC, "wf_search.hip"), os.path.join(CSRC, "wf_search_gap.hip"),
            os.path.join(CSRC, "wf_dust.hip"), os.path.join(CSRC, "wf_hits.hip"),
-           os.path.join(CSRC, "wf_order.hip"), os.path.join(CSRC, "wf_api.cpp")]
+           os.path.join(CSRC, "wf_order.hip"), os.path.join(CSRC, "wf_report.hip"),
+           os.path.join(CSRC, "wf_api.cpp")]
 DEPS = SOURCES + [os.path.join(CSRC, "wf_internal.h"), os.path.join(CSRC, "wf_device.h"),
                   os.path.join(CSRC, "wf_sparse.h"), os.path.join(CSRC, "wf_lanes.h"),
                   os.path.join(CSRC, "wf_stamps.h"), os.path.join(CSRC, "wf_attach.h"),
-                  os.path.join(CSRC, "wf_mapstore.h"), os.path.join(REPO, "include", "waafle_hip.h")]
+                  os.path.join(CSRC, "wf_mapstore.h"), os.path.join(CSRC, "wf_keys.h"), os.path.join(REPO, "include", "waafle_hip.h")]
 
 # -ffp-contract=off: no a*b+c fusion anywhere, so float64 results match numpy bit-for-bit.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-fPIC", "-shared",

@@ -56,6 +56,7 @@ struct wf_ctx {
   int64_t dump_cap = 0;            // wf_set_option(WF_OPT_DUMP_CAP), 0: the default size
   int triage = 1;                  // wf_set_option(WF_OPT_TRIAGE)
   int wave_two = 2;                // wf_set_option(WF_OPT_WAVE_TWO)
+  int search_report = 0;           // wf_set_option(WF_OPT_SEARCH_REPORT)
   wf::StagedState* staged = nullptr;
   wf::MapState* map = nullptr;     // paired-read mapper: its index and staging (wf_map_index)
   wf::OrderState* order = nullptr; // wf_order_records: its device arrays
@@ -295,6 +296,10 @@ int wf_set_option(wf_ctx* ctx, int option, int64_t value) {
     case WF_OPT_TRIAGE:
       if (value < 0 || value > 1) return fail(ctx, WF_E_BADINPUT, "WF_OPT_TRIAGE is 0 or 1");
       ctx->triage = (int)value;
+      return WF_OK;
+    case WF_OPT_SEARCH_REPORT:
+      if (value < 0 || value > 1) return fail(ctx, WF_E_BADINPUT, "WF_OPT_SEARCH_REPORT is 0 (host) or 1 (device)");
+      ctx->search_report = (int)value;
       return WF_OK;
     default:
       return fail(ctx, WF_E_BADINPUT, "unknown option %d", option);
@@ -1007,6 +1012,7 @@ static int run_search(wf_ctx* ctx, const wf::ChunkSource& src, const int64_t* of
   const wf::SearchOut out{r->capacity, r->contig, r->subject, r->minus, r->qstart, r->sstart, r->length, r->matches};
   wf::SearchStats stats{0, 0, 0};
   std::string err;
+  wf::search_set_report(ctx->map, ctx->search_report);
   const int rc = wf::search_run(ctx->map, src, off, n_subjects, rule, out, &r->n, &stats, ctx->stream, &err);
   if (rc) return fail(ctx, rc, "%s", err.c_str());
   r->seed_hits = stats.seed_hits;
@@ -1029,6 +1035,7 @@ static int run_search_gapped(wf_ctx* ctx, const wf::ChunkSource& src, const int6
   wf::SearchStats stats{0, 0, 0};
   wf::SearchGapStats gstats{0, 0};
   std::string err;
+  wf::search_set_report(ctx->map, ctx->search_report);
   const int rc = wf::search_gapped_run(ctx->map, src, off, n_subjects, rule, gp->band, gp->xdrop_gap, out, &r->n,
                                        &stats, &gstats, ctx->stream, &err);
   if (rc) return fail(ctx, rc, "%s", err.c_str());
@@ -1102,6 +1109,131 @@ int wf_search_gapped_packed(wf_ctx* ctx, const wf_search_packed_subjects* sb, co
   if (rc || !run) return rc;
   return run_search_gapped(ctx, wf::ChunkSource{nullptr, sb->lo, sb->hi, sb->nn, sb->n_words, sb->bit0}, sb->off,
                            sb->n_subjects, p, gp, r);
+}
+
+// the checks the two stand-alone reporting entries share; *run: there are records
+static int check_report_call(wf_ctx* ctx, int64_t n, int32_t min_score, int64_t capacity, bool* run) {
+  *run = false;
+  if (n < 0 || n >= (int64_t)1 << 31) return fail(ctx, WF_E_BADINPUT, "n outside [0, 2^31)");
+  if (min_score < 1) return fail(ctx, WF_E_BADINPUT, "min_score %d below 1", min_score);
+  if (capacity < 0) return fail(ctx, WF_E_BADINPUT, "negative capacity");
+  *run = n > 0;
+  return WF_OK;
+}
+
+static void widen(wf::RepBounds* B, int f, int64_t v, bool first) {
+  if (first || v < B->lo[f]) B->lo[f] = v;
+  if (first || v > B->hi[f]) B->hi[f] = v;
+}
+
+int wf_search_report(wf_ctx* ctx, const wf_report_hsps* in, wf_search_result* r) {
+  if (!ctx) return WF_E_BADINPUT;
+  if (!in || !r) return fail(ctx, WF_E_BADINPUT, "null hsps/result");
+  bool run = false;
+  int rc = check_report_call(ctx, in->n, in->min_score, r->capacity, &run);
+  if (rc) return rc;
+  if (r->capacity > 0 && (!r->contig || !r->subject || !r->minus || !r->qstart || !r->sstart || !r->length ||
+                          !r->matches))
+    return fail(ctx, WF_E_BADINPUT, "null result arrays");
+  wf::RepBounds B{};
+  if (run) {
+    if (!in->contig || !in->subject || !in->minus || !in->delta || !in->b || !in->e || !in->score)
+      return fail(ctx, WF_E_BADINPUT, "null hsp arrays");
+    for (int64_t i = 0; i < in->n; ++i) {
+      const long long k = (long long)i;
+      if (in->contig[i] < 0) return fail(ctx, WF_E_BADINPUT, "hsp %lld: contig %d", k, in->contig[i]);
+      if (in->subject[i] < 0 || in->subject[i] >= 1 << 30)
+        return fail(ctx, WF_E_BADINPUT, "hsp %lld: subject %d", k, in->subject[i]);
+      if (in->minus[i] > 1) return fail(ctx, WF_E_BADINPUT, "hsp %lld: minus is %d", k, (int)in->minus[i]);
+      const int64_t b = in->b[i], e = in->e[i], len = e - b, s3 = (int64_t)in->score[i] + 2 * len;
+      if (b < 0) return fail(ctx, WF_E_BADINPUT, "hsp %lld: b %d", k, in->b[i]);
+      if (e <= b) return fail(ctx, WF_E_BADINPUT, "hsp %lld: e %d not above b %d", k, in->e[i], in->b[i]);
+      if (s3 % 3 != 0 || s3 < 0 || s3 > 3 * len)
+        return fail(ctx, WF_E_BADINPUT, "hsp %lld: score %d is no score of %lld columns", k, in->score[i], (long long)len);
+      const int64_t v[7] = {(int64_t)in->subject[i] << 1 | in->minus[i], in->contig[i], in->delta[i], b, e,
+                            b + in->delta[i], len};
+      if (v[5] < INT32_MIN || v[5] > INT32_MAX)
+        return fail(ctx, WF_E_BADINPUT, "hsp %lld: b + delta is outside int32", k);
+      for (int f = 0; f < 7; ++f) widen(&B, f, v[f], i == 0);
+    }
+  }
+  r->n = 0;
+  r->seed_hits = r->seeds_skipped = 0;
+  r->raw_hsps = in->n;
+  if (!run) return WF_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (!ctx->map) ctx->map = wf::map_create();
+  const wf::ReportHsps h{in->n, in->min_score, in->contig, in->subject, in->minus, in->delta, in->b, in->e, in->score};
+  const wf::SearchOut out{r->capacity, r->contig, r->subject, r->minus, r->qstart, r->sstart, r->length, r->matches};
+  std::string err;
+  rc = wf::report_hsps(ctx->map, ctx->search_report != 0, h, B, out, &r->n, ctx->stream, &err);
+  if (rc) return fail(ctx, rc, "%s", err.c_str());
+  if (r->n > r->capacity)
+    return fail(ctx, WF_E_NOMEM, "%lld records, room for %lld", (long long)r->n, (long long)r->capacity);
+  return WF_OK;
+}
+
+int wf_search_report_gapped(wf_ctx* ctx, const wf_report_anchors* in, wf_search_gap_result* r) {
+  if (!ctx) return WF_E_BADINPUT;
+  if (!in || !r) return fail(ctx, WF_E_BADINPUT, "null anchors/result");
+  bool run = false;
+  int rc = check_report_call(ctx, in->n, in->min_score, r->capacity, &run);
+  if (rc) return rc;
+  if (r->capacity > 0 && (!r->contig || !r->subject || !r->minus || !r->qstart || !r->qspan || !r->sstart ||
+                          !r->sspan || !r->length || !r->matches || !r->gaps))
+    return fail(ctx, WF_E_BADINPUT, "null result arrays");
+  wf::RepBounds B{};
+  const int32_t* side[8] = {in->left_H, in->left_p, in->left_q, in->left_g, in->right_H, in->right_p, in->right_q,
+                            in->right_g};
+  if (run) {
+    bool null_side = false;
+    for (int k = 0; k < 8; ++k) null_side = null_side || !side[k];
+    if (!in->contig || !in->subject || !in->minus || !in->i0 || !in->j0 || null_side)
+      return fail(ctx, WF_E_BADINPUT, "null anchor arrays");
+    for (int64_t i = 0; i < in->n; ++i) {
+      const long long k = (long long)i;
+      if (in->contig[i] < 0) return fail(ctx, WF_E_BADINPUT, "anchor %lld: contig %d", k, in->contig[i]);
+      if (in->subject[i] < 0 || in->subject[i] >= 1 << 30)
+        return fail(ctx, WF_E_BADINPUT, "anchor %lld: subject %d", k, in->subject[i]);
+      if (in->minus[i] > 1) return fail(ctx, WF_E_BADINPUT, "anchor %lld: minus is %d", k, (int)in->minus[i]);
+      for (int sd = 0; sd < 8; sd += 4)
+        for (int f = 1; f < 4; ++f)
+          if (side[sd + f][i] < 0)
+            return fail(ctx, WF_E_BADINPUT, "anchor %lld: negative %s %c", k, sd ? "right" : "left", "Hpqg"[f]);
+      const int64_t Lp = side[1][i], Lq = side[2][i], Rp = side[5][i], Rq = side[6][i];
+      const int64_t sspan = Lp + Rp, qspan = Lq + Rq, gaps = (int64_t)side[3][i] + side[7][i];
+      const int64_t score2 = (int64_t)side[0][i] + side[4][i];
+      if ((sspan + qspan - gaps) % 2 != 0)
+        return fail(ctx, WF_E_BADINPUT, "anchor %lld: sspan + qspan - gaps is odd", k);
+      const int64_t pairs = (sspan + qspan - gaps) / 2, length = pairs + gaps, m6 = score2 + 5 * gaps + 4 * pairs;
+      if (m6 % 6 != 0 || m6 < 0 || m6 > 6 * length)
+        return fail(ctx, WF_E_BADINPUT, "anchor %lld: its sides give no number of matches in 0 .. length", k);
+      const int64_t v[wf::kRepFields] = {(int64_t)in->subject[i] << 1 | in->minus[i], in->contig[i], score2,
+                                         in->j0[i] - Lq, in->i0[i] - Lp, qspan, sspan, length, m6 / 6, gaps};
+      for (int f = 0; f < wf::kRepFields; ++f) {
+        if (f >= wf::kRepQstart && (v[f] < INT32_MIN || v[f] > INT32_MAX))
+          return fail(ctx, WF_E_BADINPUT, "anchor %lld: a field of its alignment is outside int32", k);
+        widen(&B, f, v[f], i == 0);
+      }
+    }
+  }
+  r->n = 0;
+  r->seed_hits = r->seeds_skipped = r->raw_hsps = 0;
+  r->anchors = in->n;
+  r->raw_alignments = 0;
+  if (!run) return WF_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (!ctx->map) ctx->map = wf::map_create();
+  const wf::ReportAnchors a{in->n, in->min_score, in->contig, in->subject, in->minus, in->i0, in->j0,
+                            {side[0], side[1], side[2], side[3], side[4], side[5], side[6], side[7]}};
+  const wf::SearchGapOut out{r->capacity, r->contig, r->subject, r->minus, r->qstart, r->qspan,
+                             r->sstart,   r->sspan,  r->length,  r->matches, r->gaps};
+  std::string err;
+  rc = wf::report_alns(ctx->map, ctx->search_report != 0, a, B, out, &r->n, &r->raw_alignments, ctx->stream, &err);
+  if (rc) return fail(ctx, rc, "%s", err.c_str());
+  if (r->n > r->capacity)
+    return fail(ctx, WF_E_NOMEM, "%lld records, room for %lld", (long long)r->n, (long long)r->capacity);
+  return WF_OK;
 }
 
 int wf_search_chunk_planes(wf_ctx* ctx, int strand, uint32_t* lo, uint32_t* hi, uint32_t* nn, int64_t words) {

@@ -227,6 +227,31 @@ struct SearchGapStats { int64_t anchors, raw_alignments; };
 int search_gapped_run(MapState* st, const ChunkSource& src, const int64_t* off, int64_t n_subjects, const SearchRule& rule,
                       int band, int xdrop_gap, const SearchGapOut& out, int64_t* n, SearchStats* stats,
                       SearchGapStats* gstats, hipStream_t s, std::string* err);
+// The reporting step (wf_report.hip).  RepBounds: inclusive bounds
+// of the fields a call's records can take; the device form packs every field of a sort key as
+// (value - lo) in the bits of (hi - lo).
+enum { kRepSm, kRepContig, kRepDelta, kRepB, kRepE, kRepQstartU, kRepLengthU };                 // ungapped
+enum { kRepScore2 = 2, kRepQstart, kRepSstart, kRepQspan, kRepSspan, kRepLength, kRepMatches, kRepGaps, kRepFields };
+struct RepBounds { int64_t lo[kRepFields], hi[kRepFields]; };
+// where the four search calls on st run their reporting step from now on: 0 host, 1 device
+void search_set_report(MapState* st, int report_on);
+// The stand-alone entries (wf_search_report, wf_search_report_gapped): host columns in, checked by
+// the caller, which also made B in its pass; the first min(*n, capacity) sorted records out.
+// device: the form.  0, or -2 with the message in *err.
+struct ReportHsps {
+  int64_t n; int min_score;
+  const int32_t* contig; const int32_t* subject; const uint8_t* minus; const int32_t* delta; const int32_t* b;
+  const int32_t* e; const int32_t* score;
+};
+struct ReportAnchors {
+  int64_t n; int min_score;
+  const int32_t* contig; const int32_t* subject; const uint8_t* minus; const int32_t* i0; const int32_t* j0;
+  const int32_t* side[8];                  // left H, p, q, g; right H, p, q, g
+};
+int report_hsps(MapState* st, bool device, const ReportHsps& in, const RepBounds& B, const SearchOut& out, int64_t* n,
+                hipStream_t s, std::string* err);
+int report_alns(MapState* st, bool device, const ReportAnchors& in, const RepBounds& B, const SearchGapOut& out,
+                int64_t* n, int64_t* raw_alignments, hipStream_t s, std::string* err);
 // The chunk the last search call left resident: its store words per plane, (total + 31) / 32 +
 // 2, or 0 when none is; and its planes of `strand` copied to the host (lo, hi, nn: that many
 // words each).

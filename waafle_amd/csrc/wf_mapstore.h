@@ -78,6 +78,25 @@ struct GapAnchor { int32_t sm, contig, i0, j0; };   // subject << 1 | minus; i0 
 struct GapSide { int32_t H, p, q, g; };
 struct GapRaw { GapSide left, right; };
 
+struct SearchRec { int32_t contig, subject, minus, qstart, sstart, length, matches; };
+struct GapAln {               // one gapped alignment
+  int32_t sm, contig, qstart, qspan, sstart, sspan, length, matches, gaps;
+  int64_t score2;
+};
+
+// the device form of the reporting step (wf_report.hip): grow-only
+struct ReportState {
+  DevArr<uint64_t> keys;       // [words][n] the composite sort keys
+  DevArr<uint64_t> kin, kout;  // one sort's keys
+  DevArr<uint64_t> val, run;   // a scan's input and output
+  DevArr<int32_t> perm, spare; // the sorted order and its double buffer
+  DevArr<int32_t> flag, first; // per sorted position: a flag; its group's first position
+  DevArr<int64_t> box;         // [n][4] gapped: the two intervals of the alignment at a sorted position
+  DevArr<SearchRec> rec, rec_sorted;
+  DevArr<GapAln> aln, aln_kept, aln_sorted;
+  DevArr<unsigned char> tmp;   // hipcub's scratch
+};
+
 struct SearchState {
   DevArr<unsigned char> seq, tmp;
   DevArr<int64_t> off, soff;
@@ -90,6 +109,8 @@ struct SearchState {
   DevArr<GapRaw> g_out;
   DevArr<uint32_t> planes;     // a packed chunk as uploaded: lo, hi, nn, n_words each (k_search_unpack reads it)
   int64_t resident = -1;       // bases of the chunk whose planes pk, nm hold; -1: none
+  int report_on = 0;           // WF_OPT_SEARCH_REPORT: 0 the reporting step on the host, 1 on the device
+  ReportState rep;
 };
 
 struct MapState {
@@ -141,8 +162,6 @@ struct ChunkView {
   int64_t total;              // bases of the chunk
 };
 
-struct SearchRec { int32_t contig, subject, minus, qstart, sstart, length, matches; };
-
 // (wf_map.hip)
 MapIndexView map_view(const MapState* st);
 // seq[0, total) as bit planes of (total + 31) / 32 + 2 words, the padding N; rc: the reverse
@@ -169,6 +188,43 @@ ChunkView chunk_view(const SearchState& ss, int64_t total);
 int search_records(MapState* st, const ChunkSource& src, const int64_t* off, int64_t n_subjects, const SearchRule& rule,
                    std::vector<SearchRec>* recs, SearchStats* stats, hipStream_t s, std::string* err);
 
+// ... with the reporting step on the device: the same records, *n_recs of
+// them, in st->search.rep.rec_sorted; the raw HSPs never leave the device.
+int search_records_device(MapState* st, const ChunkSource& src, const int64_t* off, int64_t n_subjects,
+                          const SearchRule& rule, int64_t* n_recs, SearchStats* stats, hipStream_t s, std::string* err);
+
+// (wf_search_gap.hip) the anchors [0, n) on the device extended into out[0, n), in launches of at
+// most 2^16 with nothing between them; the chunk of `total` bases is resident.  Enqueued on s.
+int gapped_launches(MapState* st, const GapAnchor* anchor, int64_t n, int band, int xdrop_gap, int64_t total,
+                    GapRaw* out, hipStream_t s, std::string* err);
+
+// ---- the reporting step (wf_report.hip) ---------------------
+// host forms: what search_records and search_gapped_run always did.  raw is sorted in place.
+void report_hsps_host(std::vector<SearchRaw>* raw, int min_score, std::vector<SearchRec>* recs);
+void report_alns_host(const std::vector<GapAnchor>& anchors, const std::vector<GapRaw>& raw, int min_score,
+                      std::vector<GapAln>* kept, int64_t* raw_alignments);
+// device forms.  raw / anchor, graw: device arrays of n >= 0 elements.  The records come sorted
+// in st->rep.rec_sorted / aln_sorted, *n_rec of them.  Returns after a synchronisation.
+int report_hsps_device(ReportState* R, const SearchRaw* raw, int64_t n, int min_score, const RepBounds& B,
+                       int64_t* n_rec, hipStream_t s, std::string* err);
+int report_alns_device(ReportState* R, const GapAnchor* anchor, const GapRaw* graw, int64_t n, int min_score,
+                       const RepBounds& B, int64_t* n_rec, int64_t* raw_alignments, hipStream_t s, std::string* err);
+// anchor[i] of the record rec[i], i < n (device arrays); enqueued on s
+int report_anchors(const SearchRec* rec, int64_t n, GapAnchor* anchor, hipStream_t s, std::string* err);
+// a (device) holds `have` elements worth keeping: room for `count`, the contents kept
+template <class T>
+int grow_keep(DevArr<T>& a, size_t count, size_t have, hipStream_t s, std::string* err) {
+  if (a.p && a.n >= count) return 0;
+  DevArr<T> b;
+  MAP_RC(b.ensure(std::max(count, 2 * a.n), err));
+  if (have) {
+    MAP_TRY(hipMemcpyAsync(b.p, a.p, have * sizeof(T), hipMemcpyDeviceToDevice, s));
+    MAP_TRY(hipStreamSynchronize(s));                // the old array is freed below
+  }
+  std::swap(a.p, b.p);
+  std::swap(a.n, b.n);
+  return 0;
+}
 // ---- device helpers -----------------------------------------------------------------------
 
 // A0 C1 G2 T3, anything else 4 (N); lower case counts as upper

@@ -36,6 +36,7 @@
 #include <algorithm>
 #include <string>
 
+#include "wf_keys.h"
 #include "wf_mapstore.h"
 
 namespace wf {
@@ -71,17 +72,6 @@ inline unsigned grid_of(int64_t n) { return (unsigned)((n + kOrderNT - 1) / kOrd
 __device__ __forceinline__ int64_t order_score(const OrderCols& C, int64_t i) {
   const int64_t m = C.matches[i], len = C.length[i];
   return C.gaps ? 6 * m - 4 * len - (int64_t)C.gaps[i] : 3 * m - 2 * len;
-}
-
-// v (below 2^bits) into bits [off, off + bits) of the key w[0 .. 4), w[0] the least significant word
-__device__ __forceinline__ void key_put(uint64_t (&w)[4], uint64_t v, int off, int bits) {
-  if (bits == 0) return;
-  const int word = off >> 6, sh = off & 63;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    if (k == word) w[k] |= v << sh;
-    if (k == word + 1 && sh + bits > 64) w[k] |= v >> (64 - sh);
-  }
 }
 
 __global__ __launch_bounds__(kOrderNT) void k_order_keys(OrderCols C, OrderPlan P, int64_t n, int words,
@@ -204,6 +194,44 @@ int to_host(T* dst, const T* src, int64_t n, hipStream_t s, std::string* err) {
 
 }  // namespace
 
+int key_iota(int32_t* a, int64_t n, hipStream_t s, std::string* err) {
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(k_order_iota, dim3(grid_of(n)), dim3(kOrderNT), 0, s, a, n);
+  MAP_TRY(hipGetLastError());
+  return 0;
+}
+
+int key_sort_scratch(int words, int total_bits, int n, size_t* bytes, hipStream_t s, std::string* err) {
+  *bytes = 0;
+  for (int w = 0; w < words; ++w) {
+    size_t t = 0;
+    MAP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, t, (const uint64_t*)nullptr, (uint64_t*)nullptr,
+                                               (const int32_t*)nullptr, (int32_t*)nullptr, n, 0,
+                                               std::min(64, total_bits - 64 * w), s));
+    *bytes = std::max(*bytes, t);
+  }
+  return 0;
+}
+
+int key_sort(const uint64_t* keys, int words, int total_bits, int n, uint64_t* kin_buf, uint64_t* kout, int32_t** perm,
+             int32_t** spare, void* tmp, size_t tmp_bytes, hipStream_t s, std::string* err) {
+  for (int w = 0; w < words; ++w) {
+    const uint64_t* word = keys + (size_t)w * (size_t)n;
+    const uint64_t* kin = word;                              // the first permutation is the identity
+    if (w > 0) {
+      hipLaunchKernelGGL(k_order_pick, dim3(grid_of(n)), dim3(kOrderNT), 0, s, word, (const int32_t*)*perm, (int64_t)n,
+                         kin_buf);
+      MAP_TRY(hipGetLastError());
+      kin = kin_buf;
+    }
+    size_t tb = tmp_bytes;
+    MAP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tb, kin, kout, (const int32_t*)*perm, *spare, n, 0,
+                                               std::min(64, total_bits - 64 * w), s));
+    std::swap(*perm, *spare);
+  }
+  return 0;
+}
+
 int order_run(OrderState* st, const OrderIn& in, const OrderPlan& plan, const OrderOut& out, hipStream_t s,
               std::string* err) {
   const int64_t n = in.n;                                   // 0 < n < 2^31, checked by the caller
@@ -265,22 +293,10 @@ int order_run(OrderState* st, const OrderIn& in, const OrderPlan& plan, const Or
   // the sort: least significant word first
   int32_t* perm = arr(0);
   int32_t* spare = arr(1);
-  hipLaunchKernelGGL(k_order_iota, dim3(grid), dim3(kOrderNT), 0, s, perm, n);
+  MAP_RC(key_iota(perm, n, s, err));
   if (words > 0) hipLaunchKernelGGL(k_order_keys, dim3(grid), dim3(kOrderNT), 0, s, C, plan, n, words, st->keys.p);
   MAP_TRY(hipGetLastError());
-  for (int w = 0; w < words; ++w) {
-    const uint64_t* word = st->keys.p + (size_t)w * un;
-    const uint64_t* kin = word;                              // the first permutation is the identity
-    if (w > 0) {
-      hipLaunchKernelGGL(k_order_pick, dim3(grid), dim3(kOrderNT), 0, s, word, perm, n, st->kin.p);
-      MAP_TRY(hipGetLastError());
-      kin = st->kin.p;
-    }
-    tb = st->tmp.n;
-    MAP_TRY(hipcub::DeviceRadixSort::SortPairs(st->tmp.p, tb, kin, st->kout.p, (const int32_t*)perm, spare, ni, 0,
-                                               std::min(64, total_bits - 64 * w), s));
-    std::swap(perm, spare);
-  }
+  MAP_RC(key_sort(st->keys.p, words, total_bits, ni, st->kin.p, st->kout.p, &perm, &spare, st->tmp.p, st->tmp.n, s, err));
 
   // the limit
   int64_t n_kept = n;

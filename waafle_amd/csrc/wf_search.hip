@@ -22,8 +22,10 @@
 //                    load), then the x-drop walk to the right and to the left over 32-column
 //                    mismatch words, a run of matches at a time.  A hit whose predecessor
 //                    (a - T, same diagonal) is a seed hit too gives the same HSP and is skipped.
-//   The HSPs go to the host, which sorts them per (subject, strand, contig, diagonal), counts
-//   identical ones once, drops the strictly contained and those below min_score.
+//   The reporting step (wf_report.hip) sorts the HSPs per (subject, strand, contig, diagonal),
+//   counts identical ones once, drops the strictly contained and those below min_score: on the
+//   host, to which every launch's HSPs are copied, or (SearchState::report_on)
+//   on the device, where the launches append to one array with nothing between them.
 #include <algorithm>
 #include <string>
 #include <tuple>
@@ -53,8 +55,8 @@ struct SearchArgs {
   int32_t* first;             // [nt]
   const int32_t* start;       // [nt] exclusive scan of cnt
   int h0, nh;                 // the launch: seed hits [h0, h0 + nh) of the tile
-  SearchRaw* raw;             // [kSearchLaunch]
-  unsigned long long* ctr;    // [0] HSPs written, [1] seed hits skipped
+  SearchRaw* raw;             // [kSearchLaunch]; the device form: room for every seed hit so far
+  unsigned long long* ctr;    // [0] HSPs written, [1] seed hits skipped (the device form: of the chunk)
 };
 
 struct SearchSeed {
@@ -178,7 +180,8 @@ __global__ __launch_bounds__(256) void k_search_extend(const SearchArgs A) {
   out.b = sd.a - ext_l;
   out.e = sd.a + S + ext_r;
   out.score = S + best_r + best_l;
-  A.raw[atomicAdd(&A.ctr[0], 1ull)] = out;       // at most nh <= kSearchLaunch per launch
+  // at most nh <= kSearchLaunch per launch; the device form counts on: at most the seed hits so far
+  A.raw[atomicAdd(&A.ctr[0], 1ull)] = out;
 }
 
 struct UnpackArgs {
@@ -256,9 +259,10 @@ int search_store(SearchState* ss, const ChunkSource& src, int64_t total, hipStre
   return 0;
 }
 
-// the seed hits of the chunk, extended: appended to *raw
+// the seed hits of the chunk, extended: appended to *raw; or, with raw null (the device form of
+// the reporting step), left in ss->raw, *n_raw of them
 int search_device(MapState* st, const ChunkSource& src, const int64_t* off, int64_t n, const SearchRule& rule,
-                  std::vector<SearchRaw>* raw, SearchStats* stats, hipStream_t s, std::string* err) {
+                  std::vector<SearchRaw>* raw, int64_t* n_raw, SearchStats* stats, hipStream_t s, std::string* err) {
   SearchState* ss = &st->search;
   const int64_t total = off[n];
   const int S = st->seed_len;
@@ -283,8 +287,9 @@ int search_device(MapState* st, const ChunkSource& src, const int64_t* off, int6
   MAP_RC(ss->cnt.ensure(tile_cap, err));
   MAP_RC(ss->first.ensure(tile_cap, err));
   MAP_RC(ss->start.ensure(tile_cap, err));
-  MAP_RC(ss->raw.ensure(kSearchLaunch, err));
+  if (raw) MAP_RC(ss->raw.ensure(kSearchLaunch, err));
   MAP_RC(ss->ctr.ensure(2, err));
+  if (!raw) MAP_TRY(hipMemsetAsync(ss->ctr.p, 0, 2 * sizeof(unsigned long long), s));
   MAP_RC(scan_reserve(ss->tmp, (int)tile_cap, s, err));      // the largest tile: the loop allocates nothing
   MAP_TRY(hipMemcpyAsync(ss->off.p, off, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, s));
   MAP_TRY(hipMemcpyAsync(ss->soff.p, soff.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, s));
@@ -303,7 +308,6 @@ int search_device(MapState* st, const ChunkSource& src, const int64_t* off, int6
   A.cnt = ss->cnt.p;
   A.first = ss->first.p;
   A.start = ss->start.p;
-  A.raw = ss->raw.p;
   A.ctr = ss->ctr.p;
   for (int64_t t0 = 0; t0 < 2 * NS; t0 += tile) {
     A.t0 = t0;
@@ -317,9 +321,18 @@ int search_device(MapState* st, const ChunkSource& src, const int64_t* off, int6
       *err = "more than 2^31 - 1 seed hits in one chunk";
       return -7;
     }
+    // the device form: every seed hit so far may have left an HSP (the scan's total has just
+    // synchronised, so the array can grow with its contents kept)
+    if (!raw) MAP_RC(grow_keep(ss->raw, (size_t)stats->seed_hits, (size_t)(stats->seed_hits - hits), s, err));
+    A.raw = ss->raw.p;
     for (int64_t h0 = 0; h0 < hits; h0 += kSearchLaunch) {
       A.h0 = (int)h0;
       A.nh = (int)std::min<int64_t>(kSearchLaunch, hits - h0);
+      if (!raw) {
+        hipLaunchKernelGGL(k_search_extend, dim3((unsigned)((A.nh + 255) / 256)), dim3(256), 0, s, A);
+        MAP_TRY(hipGetLastError());
+        continue;
+      }
       unsigned long long ctr[2] = {0, 0};
       MAP_TRY(hipMemsetAsync(ss->ctr.p, 0, sizeof ctr, s));
       hipLaunchKernelGGL(k_search_extend, dim3((unsigned)((A.nh + 255) / 256)), dim3(256), 0, s, A);
@@ -331,6 +344,13 @@ int search_device(MapState* st, const ChunkSource& src, const int64_t* off, int6
       raw->resize(had + got);
       if (got) MAP_TRY(hipMemcpy(raw->data() + had, ss->raw.p, got * sizeof(SearchRaw), hipMemcpyDeviceToHost));
     }
+  }
+  if (!raw) {
+    unsigned long long ctr[2] = {0, 0};
+    MAP_TRY(hipMemcpyAsync(ctr, ss->ctr.p, sizeof ctr, hipMemcpyDeviceToHost, s));
+    MAP_TRY(hipStreamSynchronize(s));
+    stats->skipped = (int64_t)ctr[1];
+    *n_raw = (int64_t)std::min<unsigned long long>(ctr[0], (unsigned long long)stats->seed_hits);
   }
   return 0;
 }
@@ -349,45 +369,54 @@ int search_records(MapState* st, const ChunkSource& src, const int64_t* off, int
   st->search.resident = -1;
   if (n_subjects == 0 || st->n_kmers == 0) return 0;
   std::vector<SearchRaw> raw;
-  const int rc = search_device(st, src, off, n_subjects, rule, &raw, stats, s, err);
+  const int rc = search_device(st, src, off, n_subjects, rule, &raw, nullptr, stats, s, err);
   if (rc) {
     (void)hipStreamSynchronize(s);
     return rc;
   }
   stats->raw_hsps = (int64_t)raw.size();
-  // per (subject, strand, contig, diagonal): by start ascending, end descending.  After the
-  // identical are counted once, an HSP is strictly contained in another exactly when an
-  // earlier one of its group ends at or after its end.
-  std::sort(raw.begin(), raw.end(), [](const SearchRaw& x, const SearchRaw& y) {
-    return std::make_tuple(x.sm, x.contig, x.delta, x.b, -x.e) < std::make_tuple(y.sm, y.contig, y.delta, y.b, -y.e);
-  });
-  using Rec = SearchRec;
-  int reach = 0;                                 // the greatest end seen in the group
-  for (size_t i = 0; i < raw.size(); ++i) {
-    const SearchRaw& x = raw[i];
-    const bool same = i > 0 && raw[i - 1].sm == x.sm && raw[i - 1].contig == x.contig && raw[i - 1].delta == x.delta;
-    if (!same) reach = 0;
-    if (same && raw[i - 1].b == x.b && raw[i - 1].e == x.e) continue;
-    const bool contained = same && reach >= x.e;
-    reach = std::max(reach, x.e);
-    if (contained || x.score < rule.min_score) continue;
-    const int length = x.e - x.b;
-    recs.push_back(Rec{x.contig, x.sm >> 1, x.sm & 1, x.b + x.delta, x.b, length, (x.score + 2 * length) / 3});
-  }
-  std::sort(recs.begin(), recs.end(), [](const Rec& x, const Rec& y) {
-    return std::make_tuple(x.contig, x.subject, x.minus, x.qstart, x.sstart, x.length) <
-           std::make_tuple(y.contig, y.subject, y.minus, y.qstart, y.sstart, y.length);
-  });
+  report_hsps_host(&raw, rule.min_score, &recs);
   return 0;
+}
+
+int search_records_device(MapState* st, const ChunkSource& src, const int64_t* off, int64_t n_subjects,
+                          const SearchRule& rule, int64_t* n_recs, SearchStats* stats, hipStream_t s, std::string* err) {
+  *n_recs = 0;
+  *stats = SearchStats{0, 0, 0};
+  st->search.resident = -1;
+  if (n_subjects == 0 || st->n_kmers == 0) return 0;
+  return synced_on_error(s, [&]() -> int {
+    int64_t n_raw = 0;
+    MAP_RC(search_device(st, src, off, n_subjects, rule, nullptr, &n_raw, stats, s, err));
+    stats->raw_hsps = n_raw;
+    // the bounds the host has: 2 x the chunk's subjects, the contigs, the store's and the chunk's
+    // bases for the diagonal and the contig position, the longest subject
+    int64_t longest = 0;
+    for (int64_t g = 0; g < n_subjects; ++g) longest = std::max(longest, off[g + 1] - off[g]);
+    RepBounds B{};
+    B.hi[kRepSm] = 2 * n_subjects - 1;
+    B.hi[kRepContig] = std::max(st->n_contigs - 1, 0);
+    B.lo[kRepDelta] = -off[n_subjects];
+    B.hi[kRepDelta] = st->total;
+    B.hi[kRepB] = B.hi[kRepE] = B.hi[kRepLengthU] = longest;
+    B.hi[kRepQstartU] = st->total;
+    return report_hsps_device(&st->search.rep, st->search.raw.p, n_raw, rule.min_score, B, n_recs, s, err);
+  });
 }
 
 int search_run(MapState* st, const ChunkSource& src, const int64_t* off, int64_t n_subjects, const SearchRule& rule,
                const SearchOut& out, int64_t* n, SearchStats* stats, hipStream_t s, std::string* err) {
   *n = 0;
   std::vector<SearchRec> recs;
-  const int rc = search_records(st, src, off, n_subjects, rule, &recs, stats, s, err);
-  if (rc) return rc;
-  *n = (int64_t)recs.size();
+  if (st->search.report_on) {                    // only the first `capacity` final records come back
+    MAP_RC(search_records_device(st, src, off, n_subjects, rule, n, stats, s, err));
+    recs.resize((size_t)std::min<int64_t>(*n, out.capacity));
+    if (!recs.empty())
+      MAP_TRY(hipMemcpy(recs.data(), st->search.rep.rec_sorted.p, recs.size() * sizeof(SearchRec), hipMemcpyDeviceToHost));
+  } else {
+    MAP_RC(search_records(st, src, off, n_subjects, rule, &recs, stats, s, err));
+    *n = (int64_t)recs.size();
+  }
   const int64_t w = std::min<int64_t>(*n, out.capacity);
   for (int64_t i = 0; i < w; ++i) {
     const SearchRec& r = recs[(size_t)i];

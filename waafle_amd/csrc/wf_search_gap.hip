@@ -19,8 +19,11 @@
 //   store word is W >= -1 (guarded, reads as N) and its second lies inside the padding.
 // Host (search_gapped_run): the ungapped records are uploaded as anchors, extended in launches
 // of at most kGapLaunch with a synchronisation each, and the reporting step of §12.5 runs in
-// C++: identical alignments once, then per (subject, strand, contig) in score order, those
-// covered by a kept one dropped.
+// C++ (report_alns_host, wf_report.hip): identical alignments once, then per (subject, strand,
+// contig) in score order, those covered by a kept one dropped.  With the reporting step on the
+// device (SearchState::report_on) the anchors are made from the device's
+// records, the launches follow one another with nothing between them (gapped_launches), and
+// only the final records come back.
 #include <algorithm>
 #include <climits>
 #include <string>
@@ -136,16 +139,6 @@ __global__ __launch_bounds__(256) void k_search_gapped(const GapArgs A) {
   if (lane == 0) A.out[a] = out;
 }
 
-struct GapAln {
-  int32_t sm, contig, qstart, qspan, sstart, sspan, length, matches, gaps;
-  int64_t score2;
-};
-
-auto aln_key(const GapAln& x) {
-  return std::make_tuple(x.sm, x.contig, -x.score2, x.qstart, x.sstart, x.qspan, x.sspan, x.length, x.matches,
-                         x.gaps);
-}
-
 int gapped_device(MapState* st, const std::vector<GapAnchor>& anchors, int band, int xdrop_gap, int64_t total,
                   std::vector<GapRaw>* raw, hipStream_t s, std::string* err) {
   SearchState* ss = &st->search;                 // search_records left the chunk in it: there are anchors
@@ -172,70 +165,91 @@ int gapped_device(MapState* st, const std::vector<GapAnchor>& anchors, int band,
 
 }  // namespace
 
+int gapped_launches(MapState* st, const GapAnchor* anchor, int64_t n, int band, int xdrop_gap, int64_t total,
+                    GapRaw* out, hipStream_t s, std::string* err) {
+  GapArgs A{};
+  A.ix = map_view(st);
+  A.ch = chunk_view(st->search, total);
+  A.W = band;
+  A.X2 = 2 * xdrop_gap;
+  for (int64_t a0 = 0; a0 < n; a0 += kGapLaunch) {
+    A.anchor = anchor + a0;
+    A.out = out + a0;
+    A.n = (int)std::min<int64_t>(kGapLaunch, n - a0);
+    hipLaunchKernelGGL(k_search_gapped, dim3((unsigned)((A.n + 3) / 4)), dim3(256), 0, s, A);
+    MAP_TRY(hipGetLastError());
+  }
+  return 0;
+}
+
+namespace {
+
+// search_gapped_run with the reporting step on the device: the kept alignments, sorted, in *kept
+// (the first `capacity` of *n)
+int gapped_on_device(MapState* st, const ChunkSource& src, const int64_t* off, int64_t n_subjects,
+                     const SearchRule& rule, int band, int xdrop_gap, int64_t capacity, std::vector<GapAln>* kept,
+                     int64_t* n, SearchStats* stats, SearchGapStats* gstats, hipStream_t s, std::string* err) {
+  SearchState* ss = &st->search;
+  int64_t n_recs = 0;
+  MAP_RC(search_records_device(st, src, off, n_subjects, rule, &n_recs, stats, s, err));
+  gstats->anchors = n_recs;
+  if (n_recs == 0) return 0;
+  return synced_on_error(s, [&]() -> int {
+    MAP_RC(ss->g_anchor.ensure((size_t)n_recs, err));
+    MAP_RC(ss->g_out.ensure((size_t)n_recs, err));
+    MAP_RC(report_anchors(ss->rep.rec_sorted.p, n_recs, ss->g_anchor.p, s, err));
+    MAP_RC(gapped_launches(st, ss->g_anchor.p, n_recs, band, xdrop_gap, off[n_subjects], ss->g_out.p, s, err));
+    int64_t longest = 0;
+    for (int64_t g = 0; g < n_subjects; ++g) longest = std::max(longest, off[g + 1] - off[g]);
+    // a side's p <= its part of the subject, q <= its part of the contig, 0 <= H <= 2 p, g <= p + q
+    const int64_t span = longest + st->total;
+    RepBounds B{};
+    B.hi[kRepSm] = 2 * n_subjects - 1;
+    B.hi[kRepContig] = std::max(st->n_contigs - 1, 0);
+    B.hi[kRepScore2] = 4 * longest;
+    B.hi[kRepQstart] = B.hi[kRepQspan] = st->total;
+    B.hi[kRepSstart] = B.hi[kRepSspan] = longest;
+    B.hi[kRepLength] = B.hi[kRepMatches] = B.hi[kRepGaps] = 2 * span;
+    MAP_RC(report_alns_device(&ss->rep, ss->g_anchor.p, ss->g_out.p, n_recs, rule.min_score, B, n,
+                              &gstats->raw_alignments, s, err));
+    kept->resize((size_t)std::min<int64_t>(*n, capacity));
+    if (!kept->empty())
+      MAP_TRY(hipMemcpy(kept->data(), ss->rep.aln_sorted.p, kept->size() * sizeof(GapAln), hipMemcpyDeviceToHost));
+    return 0;
+  });
+}
+
+}  // namespace
+
 int search_gapped_run(MapState* st, const ChunkSource& src, const int64_t* off, int64_t n_subjects, const SearchRule& rule,
                       int band, int xdrop_gap, const SearchGapOut& out, int64_t* n, SearchStats* stats,
                       SearchGapStats* gstats, hipStream_t s, std::string* err) {
   *n = 0;
   *gstats = SearchGapStats{0, 0};
-  std::vector<SearchRec> recs;
-  MAP_RC(search_records(st, src, off, n_subjects, rule, &recs, stats, s, err));
-  gstats->anchors = (int64_t)recs.size();
-  if (recs.empty()) return 0;
-  std::vector<GapAnchor> anchors(recs.size());
-  for (size_t i = 0; i < recs.size(); ++i) {
-    const SearchRec& r = recs[i];
-    const int32_t i0 = r.sstart + r.length / 2;
-    anchors[i] = GapAnchor{r.subject << 1 | r.minus, r.contig, i0, i0 + (r.qstart - r.sstart)};
-  }
-  std::vector<GapRaw> raw;
-  const int rc = gapped_device(st, anchors, band, xdrop_gap, off[n_subjects], &raw, s, err);
-  if (rc) {
-    (void)hipStreamSynchronize(s);
-    return rc;
-  }
-  std::vector<GapAln> alns(raw.size());
-  for (size_t i = 0; i < raw.size(); ++i) {
-    const GapSide &L = raw[i].left, &R = raw[i].right;
-    GapAln& x = alns[i];
-    x.sm = anchors[i].sm;
-    x.contig = anchors[i].contig;
-    x.qstart = anchors[i].j0 - L.q;
-    x.qspan = L.q + R.q;
-    x.sstart = anchors[i].i0 - L.p;
-    x.sspan = L.p + R.p;
-    x.gaps = L.g + R.g;
-    x.score2 = (int64_t)L.H + R.H;
-    const int64_t pairs = ((int64_t)x.sspan + x.qspan - x.gaps) / 2;
-    x.length = (int32_t)(pairs + x.gaps);
-    x.matches = (int32_t)((x.score2 + 5 * (int64_t)x.gaps + 4 * pairs) / 6);
-  }
-  std::sort(alns.begin(), alns.end(), [](const GapAln& x, const GapAln& y) { return aln_key(x) < aln_key(y); });
-  alns.erase(std::unique(alns.begin(), alns.end(),
-                         [](const GapAln& x, const GapAln& y) { return aln_key(x) == aln_key(y); }),
-             alns.end());
-  gstats->raw_alignments = (int64_t)alns.size();
-  // per (subject, strand, contig), in score order: dropped when a kept one covers both intervals
   std::vector<GapAln> kept;
-  size_t g0 = 0;                                 // the group's first kept one
-  for (size_t i = 0; i < alns.size(); ++i) {
-    const GapAln& x = alns[i];
-    if (i == 0 || alns[i - 1].sm != x.sm || alns[i - 1].contig != x.contig) g0 = kept.size();
-    bool covered = false;
-    for (size_t k = g0; k < kept.size() && !covered; ++k) {
-      const GapAln& y = kept[k];
-      covered = y.qstart <= x.qstart && x.qstart + x.qspan <= y.qstart + y.qspan && y.sstart <= x.sstart &&
-                x.sstart + x.sspan <= y.sstart + y.sspan;
+  if (st->search.report_on) {
+    MAP_RC(gapped_on_device(st, src, off, n_subjects, rule, band, xdrop_gap, out.capacity, &kept, n, stats, gstats, s,
+                            err));
+  } else {
+    std::vector<SearchRec> recs;
+    MAP_RC(search_records(st, src, off, n_subjects, rule, &recs, stats, s, err));
+    gstats->anchors = (int64_t)recs.size();
+    if (recs.empty()) return 0;
+    std::vector<GapAnchor> anchors(recs.size());
+    for (size_t i = 0; i < recs.size(); ++i) {
+      const SearchRec& r = recs[i];
+      const int32_t i0 = r.sstart + r.length / 2;
+      anchors[i] = GapAnchor{r.subject << 1 | r.minus, r.contig, i0, i0 + (r.qstart - r.sstart)};
     }
-    if (!covered) kept.push_back(x);
+    std::vector<GapRaw> raw;
+    const int rc = gapped_device(st, anchors, band, xdrop_gap, off[n_subjects], &raw, s, err);
+    if (rc) {
+      (void)hipStreamSynchronize(s);
+      return rc;
+    }
+    report_alns_host(anchors, raw, rule.min_score, &kept, &gstats->raw_alignments);
+    *n = (int64_t)kept.size();
   }
-  kept.erase(std::remove_if(kept.begin(), kept.end(),
-                            [&](const GapAln& x) { return x.score2 < 2 * (int64_t)rule.min_score; }),
-             kept.end());
-  std::sort(kept.begin(), kept.end(), [](const GapAln& x, const GapAln& y) {
-    return std::make_tuple(x.contig, x.sm, x.qstart, x.sstart, x.qspan, x.sspan, x.length, x.matches, x.gaps) <
-           std::make_tuple(y.contig, y.sm, y.qstart, y.sstart, y.qspan, y.sspan, y.length, y.matches, y.gaps);
-  });
-  *n = (int64_t)kept.size();
   const int64_t w = std::min<int64_t>(*n, out.capacity);
   for (int64_t i = 0; i < w; ++i) {
     const GapAln& r = kept[(size_t)i];

@@ -18,6 +18,7 @@ MODE_STAGED = 0
 MODE_LEVEL0 = 2
 MODE_WAVES = 3
 OPT_SPARSE_BIG, OPT_ATT_LIMIT, OPT_WAVE_TWO, OPT_DUMP_CAP, OPT_TRIAGE = 1, 2, 3, 4, 5   # wf_set_option
+OPT_SEARCH_REPORT = 6                                   # 0: the search's reporting step on the host, 1: on the device
 PHASES = ("waves", "attach", "segments", "decide", "big", "handover", "rollup", "triage")   # wf_phase 0..7
 N_PHASES = 8
 ABI_VERSION = 6
@@ -158,6 +159,17 @@ class WfSearchGapResult(C.Structure):
                 ("anchors", C.c_int64), ("raw_alignments", C.c_int64)]
 
 
+class WfReportHsps(C.Structure):
+    _fields_ = [("n", C.c_int64), ("min_score", C.c_int32), ("_pad", C.c_int32), ("contig", _P), ("subject", _P),
+                ("minus", _P), ("delta", _P), ("b", _P), ("e", _P), ("score", _P)]
+
+
+class WfReportAnchors(C.Structure):
+    _fields_ = [("n", C.c_int64), ("min_score", C.c_int32), ("_pad", C.c_int32), ("contig", _P), ("subject", _P),
+                ("minus", _P), ("i0", _P), ("j0", _P), ("left_H", _P), ("left_p", _P), ("left_q", _P), ("left_g", _P),
+                ("right_H", _P), ("right_p", _P), ("right_q", _P), ("right_g", _P)]
+
+
 class WfDustParams(C.Structure):
     _fields_ = [("window", C.c_int32), ("level", C.c_int32), ("_pad", C.c_int32 * 2)]
 
@@ -239,6 +251,8 @@ SIGNATURES = {
                                           C.POINTER(WfSearchParams), C.POINTER(WfSearchGapParams),
                                           C.POINTER(WfSearchGapResult)]),
     "wf_search_chunk_planes": (C.c_int, [C.c_void_p, C.c_int, _P, _P, _P, C.c_int64]),
+    "wf_search_report": (C.c_int, [C.c_void_p, C.POINTER(WfReportHsps), C.POINTER(WfSearchResult)]),
+    "wf_search_report_gapped": (C.c_int, [C.c_void_p, C.POINTER(WfReportAnchors), C.POINTER(WfSearchGapResult)]),
     "wf_search_mask": (C.c_int, [C.c_void_p, C.POINTER(WfDustParams), C.POINTER(WfDustResult)]),
     "wf_hits_from_records": (C.c_int, [C.c_void_p, C.POINTER(WfHitRecords), C.POINTER(WfHitTables),
                                        C.POINTER(WfHitsOut)]),

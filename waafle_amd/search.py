@@ -77,10 +77,15 @@ class Searcher:
     subjects and returns its records (RECORD_FIELDS, subject indices within the chunk);
     `search_gapped` runs wf_search_gapped (GAP_RECORD_FIELDS).  dust: the index holds no S-mer
     with a low-complexity base (wf_search_mask after every indexing); the searcher owns its
-    context, so no read mapper sees that index."""
+    context, so no read mapper sees that index.  report_on "device": the reporting step of every
+    search call (duplicates, containment or cover, min_score, the records' order) runs on the GPU
+    (WF_OPT_SEARCH_REPORT); the records are the same."""
 
     def __init__(self, seq, off, seed_length=21, seed_stride=8, max_seed_hits=64, xdrop=20, min_score=28,
-                 device=0, capacity=1 << 16, band=15, xdrop_gap=30, dust=False, dust_window=64, dust_level=20):
+                 device=0, capacity=1 << 16, band=15, xdrop_gap=30, dust=False, dust_window=64, dust_level=20,
+                 report_on="host"):
+        if report_on not in ("host", "device"):
+            raise SearchError("report_on is 'host' or 'device', not {!r}".format(report_on))
         self.params = L.WfSearchParams(seed_len=int(seed_length), stride=int(seed_stride),
                                        max_occ=int(max_seed_hits), xdrop=int(xdrop), min_score=int(min_score))
         self.gap_params = L.WfSearchGapParams(band=int(band), xdrop_gap=int(xdrop_gap))
@@ -93,6 +98,12 @@ class Searcher:
         # the index's own max_occ belongs to the read mapper and is not read by the search
         self.mapper = mapper.Mapper(seq, off, seed_length=int(seed_length), device=device)
         self.so, self.h = self.mapper.so, self.mapper.h
+        self.report_on = report_on
+        rc = self.so.wf_set_option(self.h, L.OPT_SEARCH_REPORT, int(report_on == "device"))
+        if rc != L.WF_OK:
+            msg = self.so.wf_last_error(self.h).decode()
+            self.close()
+            raise L.WaafleHipError(rc, msg)
         if self.dust:
             try:
                 self.apply_mask(len(seq))
@@ -549,6 +560,46 @@ def order_records_device(ctx, rec, max_target_seqs=MAX_TARGET_SEQS, gather=False
     return (order, {f: out[f][:k] for f, _ in ORDER_COLUMNS}) if gather else order
 
 
+HSP_FIELDS = (("contig", np.int32), ("subject", np.int32), ("minus", np.uint8), ("delta", np.int32),
+              ("b", np.int32), ("e", np.int32), ("score", np.int32))
+ANCHOR_FIELDS = (("contig", np.int32), ("subject", np.int32), ("minus", np.uint8), ("i0", np.int32),
+                 ("j0", np.int32)) + tuple((side + "_" + f, np.int32) for side in ("left", "right") for f in "Hpqg")
+
+
+def report_once(ctx, raw, min_score, capacity, out=None):
+    """One wf_search_report call (raw: the HSP_FIELDS columns) or, when raw has "i0", one
+    wf_search_report_gapped call (the ANCHOR_FIELDS columns), in the form the context's
+    WF_OPT_SEARCH_REPORT selects.  `ctx` as for order_records_device.  Returns (return code, full
+    record count, the records written, the call's counters); out: the arrays to write into."""
+    so, h = getattr(ctx, "so", None) or ctx.lib, ctx.h
+    gapped = "i0" in raw
+    fields = GAP_RECORD_FIELDS if gapped else RECORD_FIELDS
+    held = {f: np.ascontiguousarray(raw[f], dtype=dt) for f, dt in (ANCHOR_FIELDS if gapped else HSP_FIELDS)}
+    out = {f: np.zeros(capacity, dt) for f, dt in fields} if out is None else out
+    n = len(held["contig"])
+    if gapped:
+        a = L.WfReportAnchors(n=n, min_score=int(min_score), **{f: L.ptr(v) for f, v in held.items()})
+        r = L.WfSearchGapResult(capacity=capacity, n=-1, **{f: L.ptr(out[f]) for f, _ in fields})
+        rc = so.wf_search_report_gapped(h, C.byref(a), C.byref(r))
+    else:
+        a = L.WfReportHsps(n=n, min_score=int(min_score), **{f: L.ptr(v) for f, v in held.items()})
+        r = L.WfSearchResult(capacity=capacity, n=-1, **{f: L.ptr(out[f]) for f, _ in fields})
+        rc = so.wf_search_report(h, C.byref(a), C.byref(r))
+    full = int(r.n)
+    stats = {f: int(getattr(r, f)) for f in (GAP_STAT_FIELDS if gapped else STAT_FIELDS)}
+    return rc, full, {f: out[f][:max(0, min(full, capacity))] for f, _ in fields}, stats
+
+
+def report_records(ctx, raw, min_score):
+    """The records of the raw HSPs (or anchors with their sides) `raw`: report_once with room for
+    every one of them.  Raises lib.WaafleHipError.  Returns (records, counters)."""
+    so, h = getattr(ctx, "so", None) or ctx.lib, ctx.h
+    rc, _, out, stats = report_once(ctx, raw, min_score, max(len(raw["contig"]), 1))
+    if rc != L.WF_OK:
+        raise L.WaafleHipError(rc, so.wf_last_error(h).decode())
+    return out, stats
+
+
 def order_with(ctx, rec, max_target_seqs, order_on="host", gather=False, say=lambda *a: None):
     """The order of `rec` by the host function or, with order_on "device", on the GPU of the open
     context `ctx`; when the device has no room, one line through `say` and the host function.
@@ -618,7 +669,8 @@ def search_files(query, db, out_path, device=0, chunk_bases=CHUNK_BASES, max_tar
     magic), against the contigs `query`, written to `out_path`;
     gapped: the alignments of the gapped extension in place of the ungapped HSPs; dust: seeds
     from the contigs' unmasked S-mers only, and with dust_out the masked intervals written there;
-    order_on "device": the table's order from wf_order_records in place of order_records.
+    order_on "device": the table's order from wf_order_records in place of order_records;
+    report_on "device" (passed on to the Searcher): each chunk's reporting step on the GPU.
     Returns the searcher's counters plus rows, subjects and database bases."""
     names, seq, off = mapper.read_fasta(query)
     rec, ids, lens, stats, order = search_ordered(
@@ -725,6 +777,10 @@ def build_parser():
     g.add_argument("--order-on", choices=["host", "device"], default="host",
                    help="where the table's order and --max-target-seqs are computed: host (numpy) or\n"
                         "device (wf_order_records on the GPU; the same table)\n[default: host]")
+    g.add_argument("--report-on", choices=["host", "device"], default="host",
+                   help="where each chunk's reporting step (duplicates, contained or covered hits,\n"
+                        "--min-score, the records' order) runs: host (C++) or device (the raw hits stay\n"
+                        "on the GPU; the same table)\n[default: host]")
     g.add_argument("--chunk-bases", type=int, default=CHUNK_BASES, metavar="<int>",
                    help="subject bases per device call")
     g.add_argument("--gpu", type=int, default=0, metavar="<int>")
@@ -788,7 +844,7 @@ def main(argv=None):
                              max_seed_hits=args.max_seed_hits, xdrop=args.xdrop, min_score=args.min_score,
                              gapped=args.gapped, band=args.band, xdrop_gap=args.xdrop_gap, dust=args.dust,
                              dust_window=args.dust_window, dust_level=args.dust_level, dust_out=args.dust_out,
-                             order_on=args.order_on)
+                             order_on=args.order_on, report_on=args.report_on)
     except (inputs.InputError, OSError, L.WaafleHipError) as exc:
         die(str(exc))
     inputs.say("Finished successfully ({:,} rows from {:,} subjects; {:,} seed hits).".format(

@@ -81,7 +81,8 @@ def run(args, say):
         device=args.gpu, chunk_bases=args.chunk_bases, say=say, gapped=gapped,
         band=args.band, xdrop_gap=args.xdrop_gap, dust=args.dust, dust_window=args.dust_window,
         dust_level=args.dust_level, dust_out=args.dust_out, seed_length=args.seed_length,
-        seed_stride=args.seed_stride, max_seed_hits=args.max_seed_hits, xdrop=args.xdrop, min_score=args.min_score)
+        seed_stride=args.seed_stride, max_seed_hits=args.max_seed_hits, xdrop=args.xdrop, min_score=args.min_score,
+        report_on=args.report_on)
     if args.order_on == "device":
         # wf_order_records with gathering, on the searcher's context before it closes
         rec, ids, lens, stats, (order, cols) = search.search_ordered(
